@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of the MoMA train step (EffNet-B0 pair, 224 px, K=65536) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,10 +14,16 @@ batch fixed, per-rank queue, no data-path collective besides the gradient all-re
 Rank 0 prints ONE JSON line with the driver's contract plus
   "roofline"     : the dominant hand-written kernel (K2, one-pass InfoNCE) -- algorithmic bytes/flops per
                    launch over its HIP-event-measured mean duration inside the timed region;
-  "cpu_baseline" : the CPU restatement of the same step (oracle/step_oracle.py, pinned to the reference's
-                   trace) timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+  "cpu_baseline" : with --full only: the CPU restatement of the same step (oracle/step_oracle.py, pinned to the
+                   reference's trace) timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR then puts the model, queue and
+optimizer back into the seeded state they started from, runs the timed path for one more step on the first timed batch and
+writes what that step computed (dump_outputs below): the same inputs every run, so two runs or two builds compare output for
+output.  (The timed steps' own last outputs do not: the student's convolution weight gradients come from MIOpen's
+non-deterministic algorithms, and W + K - 1 steps of training amplify their rounding differences.)
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -77,6 +83,12 @@ def parse():
                         "how far each one got and exits 124 (default: MOMA_BENCH_LAUNCH_TIMEOUT or 420)")
     p.add_argument("--no_overlap_teacher", dest="overlap_teacher", action="store_false",
                    help="queue the teacher / key side of the step on the main stream instead of a second HIP stream")
+    p.add_argument("--full", action="store_true",
+                   help="also time the CPU restatements of the step (cpu_baseline, cpu_baseline_c1); a plain run times the GPU step only")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps, restore the seeded starting state, run the timed path for one step on the first "
+                        "timed batch and write what it computed (losses, updated student / teacher / criterion state, queue rows) "
+                        "as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     return p.parse_args()
 
 
@@ -312,6 +324,53 @@ def cpu_baseline_c1(max_seconds=10.0, max_steps=60):
     return {"value": round(B * n / dt, 2), "unit": "images/sec", "cores": torch.get_num_threads(), "kind": "port",
             "sample": f"oracle/step_oracle.py (reference op order, fp32), BASELINE configs[0]: resnet8x4 <- resnet32x4 (frozen), "
                       f"32px, B={B}, n_cls={n_cls}, K={K}, d={d} (--head None), {n} timed steps after 2 warm-up ({dt:.1f} s)"}
+
+
+DUMP_CAP = 4 << 20          # float32 elements per sampled array (16 MiB)
+
+
+def _flat_sample(tensors, cap, seed):
+    """The tensors flattened and concatenated in float32; above `cap` elements, a fixed seeded sample of `cap` of them (sorted)."""
+    import numpy as np
+    v = torch.cat([t.detach().reshape(-1).float().cpu() for t in tensors]).numpy()
+    if v.size > cap:
+        v = v[np.sort(np.random.default_rng(seed).choice(v.size, cap, replace=False))]
+    return v
+
+
+def restore_state(snapshot, modules, optimizer):
+    """Put the modules back to their state_dict snapshots (in place: the step graphs hold these tensors) and the optimizer's
+    momentum to zero (with dampening 0 the next SGD step is then the same as a first step)."""
+    with torch.no_grad():
+        for m, sd in zip(modules, snapshot):
+            m.load_state_dict(sd)
+        for st in optimizer.state.values():
+            if st.get("momentum_buffer") is not None:
+                st["momentum_buffer"].zero_()
+
+
+def dump_outputs(path, loss, loss_kd, model_s, model_t, criterion_kd, contrast, batch):
+    """What the step handed back and left behind: its loss and KD term, the updated student, EMA teacher and trainable
+    criterion modules (floating-point state in state_dict order), the queue rows it enqueued and a seeded sample of the queue."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    state = lambda m: [t for t in m.state_dict().values() if torch.is_tensor(t) and t.is_floating_point()]
+    mem = contrast.memory
+    K = mem.shape[0]
+    rows = (int(contrast.index) - batch + torch.arange(batch)) % K
+    arrays = {
+        "loss": np.asarray([float(loss)], dtype=np.float64),
+        "loss_kd": np.asarray([float(loss_kd)], dtype=np.float64),
+        "student_state": _flat_sample(state(model_s), DUMP_CAP, 1),
+        "teacher_state": _flat_sample(state(model_t), DUMP_CAP, 2),
+        "criterion_state": _flat_sample(state(criterion_kd), DUMP_CAP // 2, 3),
+        "queue_enqueued_rows": mem[rows.to(mem.device)].float().cpu().numpy(),
+        "queue_sample": _flat_sample([mem], DUMP_CAP // 4, 4),
+    }
+    assert sum(v.nbytes for v in arrays.values()) <= 64 * 10 ** 6
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(arrays)
 
 
 def heartbeat(period=60.0):
@@ -605,6 +664,9 @@ def main():
         phase("wrap_self_test")
         opt.gpu = local
         module_list = [ddp_s] + list(module_list)[1:]
+    # --dump-outputs: the seeded starting state, restored after the timed steps for the step whose outputs are written
+    dump_modules = (model_s, model_t, criterion_list[2], contrast)
+    snapshot = [copy.deepcopy(m.state_dict()) for m in dump_modules] if a.dump_outputs else None
     rec = EventRecorder()
     ops.set_event_recorder(rec)
     kev = KernelEvents()
@@ -727,6 +789,14 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         spread = [float(v) for v in (hi - lo).tolist()]
     dt = float(t.item())
+    if a.dump_outputs:
+        # untimed: one more step of the same (graph-served) path from the seeded starting state on the first timed batch
+        restore_state(snapshot, dump_modules, optimizer)
+        opt.trace = []                                  # (loss, queue pointer, loss_kd) of the step, device tensors
+        with quiet:
+            train_distill_moma(1, SyntheticLoader(1, a.batch_size, a.image_size, a.n_cls, 12345 + rank, dev), module_list,
+                               criterion_list, trainer, contrast, optimizer, opt)
+        barrier()
 
     if rank == 0:
         d = contrast.memory.shape[1]
@@ -855,7 +925,11 @@ def main():
                            ("DDP bucketed gradient all-reduce (student) + one flat async all-reduce of the "
                             "trainable criterion modules per step; per-rank queue, no data-path gather")}
         log(f"timed region: {dt:.2f} s; {out['value']} images/sec")
-        if world == 1 and not a.no_cpu_baseline:
+        if a.dump_outputs and opt.trace:
+            loss_last, _index, loss_kd_last = opt.trace[-1]
+            names = dump_outputs(a.dump_outputs, loss_last, loss_kd_last, model_s, model_t, criterion_list[2], contrast, a.batch_size)
+            log(f"outputs of the step from the seeded starting state written to {a.dump_outputs}: {', '.join(names)}")
+        if a.full and world == 1 and not a.no_cpu_baseline:
             log("timing the CPU restatement (bounded sample) ...")
             out["cpu_baseline"] = cpu_baseline(a)
             out["cpu_baseline_c1"] = cpu_baseline_c1()

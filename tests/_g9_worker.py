@@ -11,6 +11,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from tests import golden_npz
+
 
 def _sd(g, prefix):
     return {k[len(prefix):]: torch.from_numpy(g[k]) for k in g.files if k.startswith(prefix)}
@@ -28,7 +30,7 @@ def run_rank(rank, world, port, golden_path, device, out_path, prec="fp32"):
     from moma_amd.MoMA.criterion_moco_att import CMO
     from moma_amd.learning.contrast_trainer import ContrastTrainer
     dev = torch.device(device)
-    g = np.load(golden_path)
+    g = golden_npz.load(golden_path)
     B, K, d, steps = int(g["B"]), int(g["K"]), int(g["d"]), int(g["steps"])
     res = {}
     for ci in range(int(g["n_cases"])):
@@ -70,7 +72,7 @@ def run_rank(rank, world, port, golden_path, device, out_path, prec="fp32"):
 
 
 def compare(golden_path, out_path, world, atol_k, atol_logits):
-    g = np.load(golden_path)
+    g = golden_npz.load(golden_path)
     for rank in range(world):
         res = np.load(f"{out_path}.rank{rank}.npz")
         for key in res.files:

@@ -35,6 +35,8 @@ import torch.nn as nn
 
 REF = os.environ.get("MOMA_REFERENCE", "/root/reference")
 OUT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+from tests import golden_npz  # noqa: E402  (fixtures above 1 MiB are written in parts)
 
 
 def _shims():
@@ -70,7 +72,7 @@ def g1_attention():
         out[p + "d_wproj"] = att.proj.weight.grad.numpy()
         out[p + "d_bproj"] = att.proj.bias.grad.numpy()
     out["n_cases"] = np.array(len(cases))
-    np.savez_compressed(os.path.join(OUT, "g1_attention.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g1_attention.npz"), out)
 
 
 def g2_queue():
@@ -103,7 +105,7 @@ def g2_queue():
         out[p + "k"] = np.stack(k_trace)
         out[p + "all_k"] = np.stack(allk_trace)
     out["n_cases"] = np.array(len(cases))
-    np.savez_compressed(os.path.join(OUT, "g2_queue.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g2_queue.npz"), out)
 
 
 def g3_ema():
@@ -130,7 +132,7 @@ def g3_ema():
             out[p + f"r{i}"] = pb.detach().numpy().copy()
         out[p + "n"] = np.array(len(list(a.parameters())))
     out["n_cases"] = np.array(4)
-    np.savez_compressed(os.path.join(OUT, "g3_ema.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g3_ema.npz"), out)
 
 
 def g4_infonce():
@@ -164,7 +166,7 @@ def g4_infonce():
         out[p + "memory1"] = mem.memory.numpy().copy()
         out[p + "index1"] = np.array(mem.index)
     out["n_cases"] = np.array(len(cases))
-    np.savez_compressed(os.path.join(OUT, "g4_infonce.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g4_infonce.npz"), out)
 
 
 def g6_dual_queue():
@@ -189,7 +191,7 @@ def g6_dual_queue():
             out[p + f"s{s}_q"] = q.numpy(); out[p + f"s{s}_k"] = k.numpy(); out[p + f"s{s}_kt"] = kt.numpy(); out[p + f"s{s}_qt"] = qt.numpy()
             out[p + f"s{s}_ms"] = mem.memory_s.numpy().copy(); out[p + f"s{s}_mt"] = mem.memory_t.numpy().copy()
             out[p + f"s{s}_index"] = np.array(mem.index)
-    np.savez_compressed(os.path.join(OUT, "g6_dual_queue.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g6_dual_queue.npz"), out)
 
 
 def g7_mocoatt():
@@ -219,7 +221,7 @@ def g7_mocoatt():
         out[p + "logits"] = logits.detach().numpy(); out[p + "dq"] = q.grad.numpy()
         out[p + "mem1"] = mem.memory.numpy().copy(); out[p + "index"] = np.array(mem.index)
     out["n_cases"] = np.array(len(variants))
-    np.savez_compressed(os.path.join(OUT, "g7_mocoatt.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g7_mocoatt.npz"), out)
 
 
 def g5_step_trace():
@@ -360,7 +362,7 @@ def _step_trace(cases, fname, seed_off):
                 if name.startswith("embed_"):
                     out[p + "kd_final." + name] = t.numpy().copy()
     out["n_cases"] = np.array(len(cases))
-    np.savez_compressed(os.path.join(OUT, fname), **out)
+    golden_npz.save(os.path.join(OUT, fname), out)
 
 
 def g8_shuffle_bn_attn():
@@ -412,7 +414,7 @@ def g8_shuffle_bn_attn():
             if "running_mean" in name:
                 out[p + "t_after." + name] = t.numpy().copy()
     out["n_cases"] = np.array(3)
-    np.savez_compressed(os.path.join(OUT, "g8_shuffle_bn_attn.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g8_shuffle_bn_attn.npz"), out)
 
 
 def seeded_uniform_(t, gen, bound):
@@ -541,7 +543,7 @@ def g5b_step_trace_big():
         out[p + "t_final.fc.weight"] = model_t.state_dict()["fc.weight"].numpy().copy()
         out[p + "s_final.fc.weight"] = model_s.state_dict()["fc.weight"].numpy().copy()
     out["n_cases"] = np.array(len(cases))
-    np.savez_compressed(os.path.join(OUT, "g5b_step_trace_big.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g5b_step_trace_big.npz"), out)
 
 
 def _g9_worker(rank, world, port, path):
@@ -619,7 +621,7 @@ def g9_gather_w2():
                 out[k] = z[k]
         os.remove(f)
     out["n_cases"] = np.array(3)
-    np.savez_compressed(os.path.join(OUT, "g9_gather_w2.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g9_gather_w2.npz"), out)
 
 
 def g5c_step_trace_b256():
@@ -734,7 +736,7 @@ def g5c_step_trace_b256():
     out[p + "t_final.fc.weight"] = model_t.state_dict()["fc.weight"].numpy().copy()
     out[p + "s_final.fc.weight"] = model_s.state_dict()["fc.weight"].numpy().copy()
     out["n_cases"] = np.array(1)
-    np.savez_compressed(os.path.join(OUT, "g5c_step_trace_b256.npz"), **out)
+    golden_npz.save(os.path.join(OUT, "g5c_step_trace_b256.npz"), out)
 
 
 if __name__ == "__main__":

@@ -272,13 +272,21 @@ def test_bench_self_launch_parent_path_on_one_rccl_rank(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MOMA_DP", "MOMA_BENCH_SAME_DEVICE",
                                                             "MOMA_BENCH_BACKEND")}
     env.update(MOMA_BENCH_SELF_LAUNCH="1", MOMA_BENCH_FORCE_DIST="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + _SMALL, capture_output=True, text=True,
-                       timeout=900, cwd=ROOT, env=env)
+    dump = str(tmp_path / "outputs")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", dump] + _SMALL,
+                       capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), lines
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["dist"]["backend"] == "nccl" and out["dist"]["world_size"] == 1
+    assert out["steps"] == 6 and out["ms_per_step"] > 0
+    # --dump-outputs: one step's outputs from the seeded starting state, float32 / float64, finite, 64 MB at most
+    dumped = {f[:-len(".npy")]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+    assert set(dumped) == {"loss", "loss_kd", "student_state", "teacher_state", "criterion_state", "queue_enqueued_rows",
+                           "queue_sample"}, sorted(dumped)
+    assert all(v.dtype in (np.float32, np.float64) and v.size and np.isfinite(v).all() for v in dumped.values())
+    assert sum(v.nbytes for v in dumped.values()) <= 64 * 10 ** 6 and dumped["queue_enqueued_rows"].shape[0] == 32
     assert out["dist"]["dp_wrap"] == "FlatDataParallel" and np.isfinite(out["loss_mean_timed_steps"])
     assert out["config"]["step_graphs"]["timed_steps_replayed"] >= 4, out["config"]["step_graphs"]
     assert "starting 1 ranks" in r.stderr and "torch.distributed.run" not in r.stderr.split("starting 1 ranks")[1].splitlines()[0]
@@ -286,6 +294,26 @@ def test_bench_self_launch_parent_path_on_one_rccl_rank(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + _SMALL, capture_output=True, text=True,
                        timeout=300, cwd=ROOT, env={k: v for k, v in env.items() if not k.startswith("MOMA_BENCH")})
     assert r.returncode == 2 and "only 1 GPU(s) visible" in r.stderr, (r.returncode, r.stderr[-2000:])
+
+
+def test_bench_dump_outputs_repeat_across_processes(tmp_path):
+    """Two processes with the same arguments dump the same outputs up to rounding, at the benchmark's own size: the dumped step
+    starts from the seeded state on the same batch.  What may differ is the order of sums inside that one step (MIOpen's
+    weight gradients; bf16 autocast) -- not the W + K steps of training before it, whose compounded differences part the
+    runs by percents (the loss by 5 % after 25 steps)."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    dumped = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "5", "--no_cpu_baseline",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        dumped.append({f: np.load(tmp_path / run / f).astype(np.float64) for f in os.listdir(tmp_path / run)})
+    a, b = dumped
+    assert sorted(a) == sorted(b) and len(a) == 7
+    diff = {f: (float(np.abs(a[f] - b[f]).max()), float(np.abs(b[f]).max())) for f in a}
+    assert diff["loss.npy"][0] <= 1e-4 * diff["loss.npy"][1], diff
+    assert all(d <= 2e-3 * m for d, m in diff.values()), diff
 
 
 def test_bench_refuses_a_non_finite_loss(tmp_path):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import moma_oracle as O
+from tests import golden_npz
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,7 @@ def ops():
 
 
 def _g(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name))
+    return golden_npz.load(os.path.join(golden_dir, name))
 
 
 def _t(a, dtype=torch.float32):

@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn as nn
 
+from tests import golden_npz
+
 pytestmark = pytest.mark.gpu
 
 
@@ -36,7 +38,7 @@ def test_loop_matches_reference_trace(golden_dir, fixture, ci, fused, overlap):
     from moma_amd.distiller_zoo import DistillKL
 
     torch.backends.cudnn.benchmark = False
-    g = np.load(os.path.join(golden_dir, fixture))
+    g = golden_npz.load(os.path.join(golden_dir, fixture))
     p = f"c{ci}_"
     head = str(g[p + "head"])
     feat_dim = 64 if head == "None" else 32
@@ -112,7 +114,7 @@ def test_loop_bf16_policy_matches_reference_trace_big_queue(golden_dir, ci, queu
     from moma_amd import _lib
 
     torch.backends.cudnn.benchmark = False
-    g = np.load(os.path.join(golden_dir, "g5b_step_trace_big.npz"))
+    g = golden_npz.load(os.path.join(golden_dir, "g5b_step_trace_big.npz"))
     p = f"c{ci}_"
     d = int(g[p + "feat_dim"])
     lr = float(g[p + "lr"])
@@ -185,7 +187,7 @@ def test_loop_bf16_policy_matches_reference_trace_bench_batch(golden_dir, prec, 
     from moma_amd.distiller_zoo import DistillKL
 
     torch.backends.cudnn.benchmark = False
-    g = np.load(os.path.join(golden_dir, "g5c_step_trace_b256.npz"))
+    g = golden_npz.load(os.path.join(golden_dir, "g5c_step_trace_b256.npz"))
     p = "c0_"
     d, B, steps, lr = int(g[p + "feat_dim"]), int(g[p + "B"]), int(g[p + "steps"]), float(g[p + "lr"])
     opt = argparse.Namespace(distill="moma", head="mlp", feat_dim=d, attn="self", mem="MoCo", nce_k=K_BIG, nce_t=0.15,
@@ -309,7 +311,7 @@ def test_shuffle_bn_attn_matches_reference(golden_dir, ci, prec):
     from moma_amd.MoMA.criterion_moco_att import CMO
     from moma_amd.learning.contrast_trainer import ContrastTrainer
     torch.backends.cudnn.benchmark = False
-    g = np.load(os.path.join(golden_dir, "g8_shuffle_bn_attn.npz"))
+    g = golden_npz.load(os.path.join(golden_dir, "g8_shuffle_bn_attn.npz"))
     p = f"c{ci}_"
     attn, head, d = str(g[p + "attn"]), str(g[p + "head"]), int(g[p + "d"])
     opt = argparse.Namespace(head=head, s_dim=64, t_dim=64, feat_dim=d, attn=attn, local_rank=0, node_rank=0, ngpus_per_node=1,

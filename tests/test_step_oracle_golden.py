@@ -10,6 +10,7 @@ import torch
 
 from oracle.step_oracle import OracleCMO, OracleMoCo, StepOracle
 from moma_amd.backbones.resnet_cifar import resnet8
+from tests import golden_npz
 
 
 def _sd(g, prefix):
@@ -21,7 +22,7 @@ def _sd(g, prefix):
                                         ("g10_step_trace_heads.npz", 0), ("g10_step_trace_heads.npz", 1)])
 def test_step_trace_matches_reference(golden_dir, fixture, ci):
     torch.set_num_threads(1)
-    g = np.load(os.path.join(golden_dir, fixture))
+    g = golden_npz.load(os.path.join(golden_dir, fixture))
     p = f"c{ci}_"
     head = str(g[p + "head"])
     feat_dim = 64 if head == "None" else 32
@@ -81,7 +82,7 @@ def test_step_trace_big_queue_matches_reference(golden_dir):
     loss AND per-step loss_kd, pointer, the enqueued rows of the final queue."""
     from tests.g5b_util import K_BIG, batches, big_queue, fill_attention_, sd
     torch.set_num_threads(8)
-    g = np.load(os.path.join(golden_dir, "g5b_step_trace_big.npz"))
+    g = golden_npz.load(os.path.join(golden_dir, "g5b_step_trace_big.npz"))
     ci = 2
     p = f"c{ci}_"
     d = int(g[p + "feat_dim"])
@@ -113,7 +114,7 @@ def test_step_trace_bench_batch_matches_reference(golden_dir):
     against the reference's own per-step total loss and loss_kd, the pointer and a sample of the enqueued rows."""
     from tests.g5b_util import K_BIG, batches, big_queue, fill_attention_, sd
     torch.set_num_threads(8)
-    g = np.load(os.path.join(golden_dir, "g5c_step_trace_b256.npz"))
+    g = golden_npz.load(os.path.join(golden_dir, "g5c_step_trace_b256.npz"))
     p = "c0_"
     d, B, steps = int(g[p + "feat_dim"]), int(g[p + "B"]), int(g[p + "steps"])
     ms, mt = resnet8(num_classes=100), resnet8(num_classes=100)
@@ -143,7 +144,7 @@ def test_shuffle_bn_attn_oracle_matches_reference(golden_dir, ci):
     import torch.nn as nn
     from oracle.step_oracle import OracleAttention, _head, shuffle_bn_attn
     torch.set_num_threads(1)
-    g = np.load(os.path.join(golden_dir, "g8_shuffle_bn_attn.npz"))
+    g = golden_npz.load(os.path.join(golden_dir, "g8_shuffle_bn_attn.npz"))
     p = f"c{ci}_"
     attn, head, d = str(g[p + "attn"]), str(g[p + "head"]), int(g[p + "d"])
     mt = resnet8(num_classes=10)
