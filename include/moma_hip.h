@@ -194,6 +194,48 @@ int moma_infonce_fused_multi(const moma_infonce_term_t* terms, int n_terms, int 
                              void* workspace, size_t workspace_bytes, int qdtype, int prec, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CRD  Contrastive Representation Distillation (`--distill crd`) over two n_data x d memory banks addressed by sample index
+ *      -- replaces ContrastMemory.forward (crd/memory.py:23-79: index_select -> [B,K1,d] copy -> bmm -> exp -> div, per side,
+ *      then the momentum update of the banks) and ContrastLoss.forward (crd/criterion.py:57-74) with their autograd backward.
+ *
+ *   K1 = nce_k + 1;  idx [B,K1] int64, column 0 = the sample's own index;  c = nce_k / n_data;  eps = 1e-7;
+ *   side 1 = (v1 = student embedding, bank memory_v2), side 2 = (v2 = teacher embedding, bank memory_v1).  Per side:
+ *       s[b,j] = <M[idx[b,j]], v[b]>      e[b,j] = exp(s[b,j] / T)      x[b,j] = e[b,j] / Z
+ *       loss   = -( sum_b log(x[b,0] / (x[b,0] + c + eps)) + sum_b sum_{j>=1} log(c / (x[b,j] + c + eps)) ) / B
+ *       dv[b,:] = d loss / d v[b] = sum_j g[b,j] x[b,j] / T * M[idx[b,j],:],
+ *                 g[b,0] = -(1/x[b,0] - 1/(x[b,0] + c + eps)) / B,   g[b,j>=1] = 1 / (x[b,j] + c + eps) / B
+ *   All operands fp32; v*, memory_*, dv*, out_*, dout_* 16-byte aligned; d a multiple of 4, 4 <= d <= 2048; B <= 65535;
+ *   K1 >= 2; T > 0.  Z [2] (side 1, side 2) is a DEVICE pair: with set_z != 0 a statistics pass over the same gather writes
+ *   Z = mean(e) * n_data per side first (crd/memory.py:50-57) and the main pass reads it; with set_z == 0 Z is read as it stands.
+ *   Indices are data: an entry of idx (or y) outside [0, n_data) never becomes an address -- it contributes nothing (its score is
+ *   written as 0) and 1 is stored into *bad_index, which the caller zeroes and reads where it synchronises anyway.
+ *   workspace: moma_crd_workspace_bytes(B, d, K1) for each of the three gather calls.  Per-wave partial sums meet in a second
+ *   launch in a fixed order: no atomics, bitwise reproducible.
+ *
+ * moma_crd_fused      both sides in one pass: loss [2] (side 1, side 2; the CRD loss is their sum) and dv1 / dv2 [B,d] (both or
+ *                     neither: NULL, NULL = forward only).  Every bank row is fetched once per (b, j, side).
+ * moma_crd_scores     the materialised form ContrastMemory.forward returns: out_v1 = x of side 1, out_v2 = x of side 2, [B,K1].
+ * moma_crd_scores_bwd its backward: dv[b,:] = sum_j dout[b,j] * out[b,j] / T * M[idx[b,j],:] per side.
+ * moma_crd_update     crd/memory.py:64-77 for both banks in one launch: for i < B, r = M[y[i]] * momentum + v[i] * (1 - momentum),
+ *                     M[y[i]] = r / sqrt(sum r^2) with (memory_v1, v1) and (memory_v2, v2).  It reads the PRE-update row: issue it
+ *                     behind the gather of the same step (same stream).  A y repeated inside the batch: the last one in batch
+ *                     order wins, as in a serial index_copy_.
+ * ------------------------------------------------------------------------------------------- */
+size_t moma_crd_workspace_bytes(int B, int d, int K1);
+int moma_crd_fused(const float* v1, const float* v2, const float* memory_v1, const float* memory_v2, const int64_t* idx,
+                   int B, int d, int K1, int64_t n_data, float T, float* Z, int set_z, float* loss, float* dv1, float* dv2,
+                   int32_t* bad_index, void* workspace, size_t workspace_bytes, moma_stream_t stream);
+int moma_crd_scores(const float* v1, const float* v2, const float* memory_v1, const float* memory_v2, const int64_t* idx,
+                    int B, int d, int K1, int64_t n_data, float T, float* Z, int set_z, float* out_v1, float* out_v2,
+                    int32_t* bad_index, void* workspace, size_t workspace_bytes, moma_stream_t stream);
+int moma_crd_scores_bwd(const float* dout_v1, const float* dout_v2, const float* out_v1, const float* out_v2,
+                        const float* memory_v1, const float* memory_v2, const int64_t* idx, int B, int d, int K1,
+                        int64_t n_data, float T, float* dv1, float* dv2, int32_t* bad_index, void* workspace,
+                        size_t workspace_bytes, moma_stream_t stream);
+int moma_crd_update(float* memory_v1, float* memory_v2, const float* v1, const float* v2, const int64_t* y, int B, int d,
+                    int64_t n_data, float momentum, int32_t* bad_index, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1  batch-token multi-head attention -- replaces Attention.forward
  *     (MoMA/criterion_moco_att.py:153-167) and its autograd backward.
  *     x [N,d] -> qkv = x Wqkv^T + bqkv -> per head softmax(q k^T * hd^-1/2) v -> y = a Wproj^T + bproj.

@@ -45,7 +45,12 @@ SIGNATURES = {
     "moma_infonce_fused_enqueue": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _z, _i, _i, _p, _i, _l, _p, _p, _p, _p, _p]),
     "moma_infonce_fused_multi_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "moma_infonce_fused_multi": (_i, [_p, _i, _i, _i, _i, _f, _p, _z, _i, _i, _p]),
-    "moma_mha_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "moma_crd_workspace_bytes": (_z, [_i, _i, _i]),
+    "moma_crd_fused": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "moma_crd_scores": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _p, _i, _p, _p, _p, _p, _z, _p]),
+    "moma_crd_scores_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _p, _p, _p, _p, _z, _p]),
+    "moma_crd_update": (_i, [_p, _p, _p, _p, _p, _i, _i, _l, _f, _p, _p]),
+    "moma_mha_fwd": (_i,[_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "moma_mha_saved_state": (_i, [_i, _i, _i, _i]),
     "moma_mha_pack_bytes": (_z, [_i]),
     "moma_mha_pack_weights": (_i, [_p, _p, _p, _i, _i, _p]),

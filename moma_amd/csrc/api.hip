@@ -567,4 +567,77 @@ int moma_se_gate_bwd(const void* x, const void* s, const void* dout, void* dx, v
     return rc != MOMA_OK ? rc : hip_rc(launch_se_gate_bwd(x, s, dout, dx, ds, NC, HW, dtype, (hipStream_t)stream));
 }
 
+// ---- CRD ------------------------------------------------------------------------------------------------------------------
+static int crd_check(int B, int d, int K1, int64_t n_data, float T) {
+    if (B <= 0 || d < 4 || d % 4 != 0 || K1 < 2 || n_data <= 0 || !(T > 0.f)) return MOMA_E_SHAPE;
+    if (d > 2048 || B > 65535) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+static bool crd_misaligned(const void* a, const void* b, const void* c, const void* d, const void* e = nullptr,
+                           const void* f = nullptr, const void* g = nullptr, const void* h = nullptr) {
+    return misaligned(a, 16) || misaligned(b, 16) || misaligned(c, 16) || misaligned(d, 16) || misaligned(e, 16) ||
+           misaligned(f, 16) || misaligned(g, 16) || misaligned(h, 16);
+}
+
+size_t moma_crd_workspace_bytes(int B, int d, int K1) {
+    if (crd_check(B, d, K1, 1, 1.f) != MOMA_OK) return 0;
+    return crd_workspace_bytes(B, d, K1);
+}
+
+int moma_crd_fused(const float* v1, const float* v2, const float* memory_v1, const float* memory_v2, const int64_t* idx,
+                   int B, int d, int K1, int64_t n_data, float T, float* Z, int set_z, float* loss, float* dv1, float* dv2,
+                   int32_t* bad_index, void* workspace, size_t workspace_bytes, moma_stream_t stream) {
+    if (!v1 || !v2 || !memory_v1 || !memory_v2 || !idx || !Z || !loss || !bad_index || !workspace) return MOMA_E_NULL;
+    if ((dv1 == nullptr) != (dv2 == nullptr)) return MOMA_E_NULL;
+    const int rc = crd_check(B, d, K1, n_data, T);
+    if (rc != MOMA_OK) return rc;
+    if (crd_misaligned(v1, v2, memory_v1, memory_v2, dv1, dv2, workspace) || misaligned(idx, 8) || misaligned(Z, 4) ||
+        misaligned(loss, 4) || misaligned(bad_index, 4))
+        return MOMA_E_ALIGN;
+    if (workspace_bytes < crd_workspace_bytes(B, d, K1)) return MOMA_E_WORKSPACE;
+    return hip_rc(launch_crd_fused(v1, v2, memory_v1, memory_v2, idx, B, d, K1, n_data, T, Z, set_z, loss, dv1, dv2, bad_index,
+                                   workspace, (hipStream_t)stream));
+}
+
+int moma_crd_scores(const float* v1, const float* v2, const float* memory_v1, const float* memory_v2, const int64_t* idx,
+                    int B, int d, int K1, int64_t n_data, float T, float* Z, int set_z, float* out_v1, float* out_v2,
+                    int32_t* bad_index, void* workspace, size_t workspace_bytes, moma_stream_t stream) {
+    if (!v1 || !v2 || !memory_v1 || !memory_v2 || !idx || !Z || !out_v1 || !out_v2 || !bad_index || !workspace) return MOMA_E_NULL;
+    const int rc = crd_check(B, d, K1, n_data, T);
+    if (rc != MOMA_OK) return rc;
+    if (crd_misaligned(v1, v2, memory_v1, memory_v2, workspace) || misaligned(idx, 8) || misaligned(Z, 4) ||
+        misaligned(out_v1, 4) || misaligned(out_v2, 4) || misaligned(bad_index, 4))
+        return MOMA_E_ALIGN;
+    if (workspace_bytes < crd_workspace_bytes(B, d, K1)) return MOMA_E_WORKSPACE;
+    return hip_rc(launch_crd_scores(v1, v2, memory_v1, memory_v2, idx, B, d, K1, n_data, T, Z, set_z, out_v1, out_v2, bad_index,
+                                    workspace, (hipStream_t)stream));
+}
+
+int moma_crd_scores_bwd(const float* dout_v1, const float* dout_v2, const float* out_v1, const float* out_v2,
+                        const float* memory_v1, const float* memory_v2, const int64_t* idx, int B, int d, int K1,
+                        int64_t n_data, float T, float* dv1, float* dv2, int32_t* bad_index, void* workspace,
+                        size_t workspace_bytes, moma_stream_t stream) {
+    if (!dout_v1 || !dout_v2 || !out_v1 || !out_v2 || !memory_v1 || !memory_v2 || !idx || !dv1 || !dv2 || !bad_index || !workspace)
+        return MOMA_E_NULL;
+    const int rc = crd_check(B, d, K1, n_data, T);
+    if (rc != MOMA_OK) return rc;
+    if (crd_misaligned(memory_v1, memory_v2, dv1, dv2, workspace) || misaligned(idx, 8) || misaligned(dout_v1, 4) ||
+        misaligned(dout_v2, 4) || misaligned(out_v1, 4) || misaligned(out_v2, 4) || misaligned(bad_index, 4))
+        return MOMA_E_ALIGN;
+    if (workspace_bytes < crd_workspace_bytes(B, d, K1)) return MOMA_E_WORKSPACE;
+    return hip_rc(launch_crd_scores_bwd(dout_v1, dout_v2, out_v1, out_v2, memory_v1, memory_v2, idx, B, d, K1, n_data, T, dv1, dv2,
+                                        bad_index, workspace, (hipStream_t)stream));
+}
+
+int moma_crd_update(float* memory_v1, float* memory_v2, const float* v1, const float* v2, const int64_t* y, int B, int d,
+                    int64_t n_data, float momentum, int32_t* bad_index, moma_stream_t stream) {
+    if (!memory_v1 || !memory_v2 || !v1 || !v2 || !y || !bad_index) return MOMA_E_NULL;
+    if (B <= 0 || d <= 0 || n_data <= 0) return MOMA_E_SHAPE;
+    if (d > 2048 || B > 65535) return MOMA_E_UNSUPPORTED;
+    if (misaligned(memory_v1, 4) || misaligned(memory_v2, 4) || misaligned(v1, 4) || misaligned(v2, 4) || misaligned(y, 8) ||
+        misaligned(bad_index, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_crd_update(memory_v1, memory_v2, v1, v2, y, B, d, n_data, momentum, bad_index, (hipStream_t)stream));
+}
+
 }  // extern "C"

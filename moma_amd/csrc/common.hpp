@@ -124,6 +124,20 @@ hipError_t launch_prefetch(const void* p, size_t bytes, hipStream_t st);
 hipError_t launch_widen_bf16(const void* src, float* dst, size_t n, hipStream_t st);      // bf16 -> fp32, n elements (src 16-B aligned)
 hipError_t launch_ema(const int64_t* table, int n_tensors, int64_t total_blocks, float m, float om, hipStream_t st);
 
+// ---- crd.hip (CRD: gather-contrast over two sample-indexed memory banks) ---------------------------
+size_t crd_workspace_bytes(int B, int d, int K1);
+hipError_t launch_crd_fused(const float* v1, const float* v2, const float* memory_v1, const float* memory_v2, const int64_t* idx,
+                            int B, int d, int K1, int64_t n_data, float T, float* Z, int set_z, float* loss, float* dv1, float* dv2,
+                            int32_t* bad, void* ws, hipStream_t st);
+hipError_t launch_crd_scores(const float* v1, const float* v2, const float* memory_v1, const float* memory_v2, const int64_t* idx,
+                             int B, int d, int K1, int64_t n_data, float T, float* Z, int set_z, float* out_v1, float* out_v2,
+                             int32_t* bad, void* ws, hipStream_t st);
+hipError_t launch_crd_scores_bwd(const float* dout_v1, const float* dout_v2, const float* out_v1, const float* out_v2,
+                                 const float* memory_v1, const float* memory_v2, const int64_t* idx, int B, int d, int K1,
+                                 int64_t n_data, float T, float* dv1, float* dv2, int32_t* bad, void* ws, hipStream_t st);
+hipError_t launch_crd_update(float* memory_v1, float* memory_v2, const float* v1, const float* v2, const int64_t* y, int B, int d,
+                             int64_t n_data, float momentum, int32_t* bad, hipStream_t st);
+
 // ---- infonce_fused.hip (one-pass flash-style kernel) ----------------------------------------------
 bool infonce_flash_supported(int B, int d, int K, int qdtype, int prec);
 size_t infonce_flash_workspace_bytes(int B, int d, int K);

@@ -9,6 +9,10 @@ performance-only: the per-step `.item()` host syncs (:351,355) are deferred to p
 their grads are None either way -- Q6); the KD term uses the one-pass fused kernel unless
 opt.moma_fused is False, in which case the reference call sequence contrast(...) -> CrossEntropyLoss runs
 on materialised logits.
+
+`--distill crd` (reference :246-262, :303-306): the loader yields (images, labels, index, contrast_idx); the KD term is
+CRDLoss(feat_s[-1], feat_t[-1], index, contrast_idx) with feat_t from the teacher's single no-grad forward.  No EMA, no
+Shuffle-BN, the teacher stays frozen; the step is eager (not served from HIP graphs).
 """
 from __future__ import print_function
 
@@ -80,7 +84,7 @@ class MomaStep:
         self_mix / self_nomix, MoCo memory, per-rank Shuffle-BN; fp16 + GradScaler when the optimizer takes the scale and the found-inf flag on the
         device -- torch's fused SGD, what build_training makes for --amp fp16: the captured backward multiplies by the scaler's
         device tensor, `scaler.step / update` stay eager behind the graphs and read nothing back).  Everything else keeps the
-        eager loop."""
+        eager loop -- `--distill crd` included: its step (gather kernels + bank update between forward and backward) is eager."""
         o = self.opt
         scaler_ok = self.scaler is None or bool(getattr(self.optimizer, "_step_supports_amp_scaling", False))
         # (round 6: also --attn self_mix / self_nomix -- the key encoding with the attention in front of the un-shuffle,
@@ -98,7 +102,9 @@ class MomaStep:
         """teacher forward #1 (:270-272), then the moma branch's no-grad part (:309-320, :327-329)."""
         opt, trainer, criterion_kd, model_t = self.opt, self.trainer, self.criterion_kd, self.model_t
         with self.autocast(), torch.no_grad():
-            _, lt = teacher(images, is_feat=True)
+            ft, lt = teacher(images, is_feat=True)
+        if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
+            return lt.float(), ft[-1].float(), None
         if opt.distill != "moma":
             return lt.float(), None, None
         student = _unwrap(self.model_s)
@@ -146,6 +152,8 @@ class MomaStep:
         logit_s = logit_s.float()
         out = {"loss_cls": self.criterion_cls(logit_s, labels), "loss_div": self.criterion_div(logit_s, logit_t), "qp": None}
         f_s = None
+        if opt.distill == "crd":
+            f_s = feat_s[-1].float()                                                      # (:304)
         if opt.distill == "moma":
             with self.autocast():
                 f_s = criterion_kd.embed_s(feat_s[-1])                                    # (:323-324)
@@ -202,6 +210,9 @@ class MomaStep:
         opt, trainer, contrast, criterion_kd = self.opt, self.trainer, self.contrast, self.criterion_kd
         if opt.distill == "kd":
             return 0
+        if opt.distill == "crd":                                                          # (:303-306) f_t rides in fw["k"]
+            with self.autocast():
+                return criterion_kd(fw["f_s"], fw["k"], fw["index"], fw["contrast_idx"]).float()
         if opt.distill != "moma":
             raise NotImplementedError(opt.distill)
         f_s, k, all_k, qp = fw["f_s"], fw["k"], fw["all_k"], fw["qp"]
@@ -243,8 +254,9 @@ class MomaStep:
             loss.backward()
         return loss
 
-    def run_eager(self, images, labels, teacher):
+    def run_eager(self, images, labels, teacher, index=None, contrast_idx=None):
         fw = self.forward_part(images, labels, teacher)
+        fw.update(index=index, contrast_idx=contrast_idx)          # (--distill crd: sample indices of the batch and its negatives)
         loss_kd = self.kd_term(fw)
         loss = self.backward_part(fw, loss_kd)
         return loss.detach(), (loss_kd.detach() if torch.is_tensor(loss_kd) else loss_kd), fw["acc"]
@@ -268,14 +280,14 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             if torch.cuda.is_available() else torch.device("cpu")
     step = MomaStep(module_list, criterion_list, trainer, contrast, optimizer, opt, dev)
     single_rank = bool(getattr(trainer, "grad_sync_single_rank", False))
-    sync_criterion = opt.distill == "moma" and (getattr(opt, "world_size", 1) > 1 or single_rank)
+    sync_criterion = opt.distill in ("moma", "crd") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
     flat_dp = isinstance(model_s, FlatDataParallel)
     flat_params = None
     if flat_dp:
         # learning/ddp.py: ONE flat all-reduce per step behind the backward -- the student's gradients and those of the trainable
         # criterion modules (atts_q / embed_s: not under any wrapper, un-synchronised in the reference)
         flat_params = model_s.grad_params()
-        if opt.distill == "moma":
+        if opt.distill in ("moma", "crd"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank)
             flat_params = flat_params + [p for p in criterion_kd.parameters() if p.requires_grad]
     elif sync_criterion:
         # stock DDP on the student: one flat all-reduce per step for the trainable criterion modules, launched from autograd
@@ -312,7 +324,13 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
 
     end = time.time()
     for idx, data in enumerate(train_loader):
-        images, labels = data
+        index = contrast_idx = None
+        if opt.distill == "crd":
+            images, labels, index, contrast_idx = data
+            index = index.to(dev, non_blocking=True)
+            contrast_idx = contrast_idx.to(dev, non_blocking=True)
+        else:
+            images, labels = data
         images = images.to(dev, non_blocking=True)
         labels = labels.to(dev, non_blocking=True)
         if getattr(opt, "channels_last", False):
@@ -321,7 +339,7 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
         # =================== forward, KD term, backward =====================
         res = runner.step(images, labels) if runner is not None else None      # None: this step is not (yet) served from graphs
         if res is None:
-            res = step.run_eager(images, labels, teacher)
+            res = step.run_eager(images, labels, teacher, index, contrast_idx)
         loss, loss_kd, acc = res
         losses.update(loss, images.size(0))
         if trace is not None:           # optional per-step record (tests / benchmarking), device tensors
@@ -354,6 +372,8 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             print("Epoch: [{0}][{1}/{2}]\tGPU {3}\tTime: {bt:.3f}\tLoss {loss:.4f}\tAcc@1 {acc:.3f}".format(
                 epoch, idx, n_batch, opt.gpu, bt=batch_time.avg, loss=float(losses.avg), acc=float(top1.avg)))
             sys.stdout.flush()
+    if opt.distill == "crd":
+        criterion_kd.contrast.check_indices()      # (float(...) below synchronises anyway: the one read of the index flag per epoch)
     return float(top1.avg), float(losses.avg)
 
 

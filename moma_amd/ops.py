@@ -841,3 +841,149 @@ def plane_mean(x):
 def se_gate(x, s):
     """x * sigmoid(s) with s [N,C,1,1]."""
     return _SEGate.apply(x, s)
+
+
+# ------------------------------------------------------------------------------------------------
+# CRD: gather-contrast over two sample-indexed memory banks   (crd/memory.py:23-79, crd/criterion.py:57-74)
+# ------------------------------------------------------------------------------------------------
+def _crd_check(v1, v2, memory_v1, memory_v2, idx, n_data, Z, bad):
+    _dev(v1, "v1"); _dev(v2, "v2"); _dev(memory_v1, "memory_v1"); _dev(memory_v2, "memory_v2")
+    _dev(idx, "idx", torch.int64); _dev(Z, "Z"); _dev(bad, "bad_index", torch.int32)
+    if (v1.dim() != 2 or v1.shape != v2.shape or memory_v1.dim() != 2 or memory_v1.shape != memory_v2.shape
+            or memory_v1.shape[1] != v1.shape[1] or idx.dim() != 2 or idx.shape[0] != v1.shape[0]):
+        raise ValueError(f"shape mismatch: v1 {tuple(v1.shape)} v2 {tuple(v2.shape)} memory_v1 {tuple(memory_v1.shape)} "
+                         f"memory_v2 {tuple(memory_v2.shape)} idx {tuple(idx.shape)}")
+    if int(n_data) != memory_v1.shape[0]:
+        raise ValueError(f"n_data {n_data} != rows of the banks {memory_v1.shape[0]}")
+    if Z.numel() != 2 or bad.numel() != 1:
+        raise ValueError("Z must hold 2 floats (side 1, side 2) and bad_index one int32")
+
+
+def _crd_workspace(lib, B, d, K1, dev):
+    n = lib.moma_crd_workspace_bytes(B, d, K1)
+    if n == 0:
+        raise MomaHipError(f"moma_crd: unsupported shape B={B} d={d} K1={K1} (d a multiple of 4 up to 2048, nce_k >= 1)")
+    return torch.empty(n, device=dev, dtype=torch.uint8), n
+
+
+class _CRDFused(torch.autograd.Function):
+    """Both sides in one gather pass: loss [2] and d loss / d v1, d loss / d v2 from the rows the pass already holds."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, memory_v1, memory_v2, idx, T, n_data, Z, set_z, bad):
+        lib = _lib.load()
+        v1 = v1.contiguous() if isinstance(v1, torch.Tensor) else v1
+        v2 = v2.contiguous() if isinstance(v2, torch.Tensor) else v2
+        _crd_check(v1, v2, memory_v1, memory_v2, idx, n_data, Z, bad)
+        B, d = v1.shape
+        K1 = idx.shape[1]
+        dev = v1.device
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss = torch.empty(2, device=dev, dtype=torch.float32)
+        dv1 = torch.empty(B, d, device=dev, dtype=torch.float32) if need_grad else None
+        dv2 = torch.empty(B, d, device=dev, dtype=torch.float32) if need_grad else None
+        ws, ws_bytes = _crd_workspace(lib, B, d, K1, dev)
+        with _timed("moma_crd_fused"):
+            check(lib.moma_crd_fused(_ptr(v1), _ptr(v2), _ptr(memory_v1), _ptr(memory_v2), _ptr(idx), B, d, K1, int(n_data),
+                                     float(T), _ptr(Z), int(bool(set_z)), _ptr(loss), _ptr(dv1), _ptr(dv2), _ptr(bad), _ptr(ws),
+                                     ws_bytes, _stream()), "moma_crd_fused")
+        if need_grad:
+            ctx.save_for_backward(dv1, dv2)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dv1, dv2 = ctx.saved_tensors
+        return (dv1 * g[0] if ctx.needs_input_grad[0] else None, dv2 * g[1] if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None, None, None)
+
+
+def crd_fused(v1, v2, memory_v1, memory_v2, idx, T: float, n_data: int, Z, set_z: bool, bad=None) -> torch.Tensor:
+    """-> loss [2] (side 1: v1 against memory_v2, side 2: v2 against memory_v1); the CRD loss is loss.sum().
+    Z [2] float32 on the device: written first when set_z, read otherwise.  bad: int32 [1] on the device, set to 1 when an entry
+    of idx is not a row of the banks (a fresh zero when None: the caller cannot read it then)."""
+    if bad is None and isinstance(v1, torch.Tensor) and v1.is_cuda:
+        bad = torch.zeros(1, device=v1.device, dtype=torch.int32)
+    return _CRDFused.apply(v1, v2, memory_v1, memory_v2, idx, float(T), int(n_data), Z, bool(set_z), bad)
+
+
+class _CRDScores(torch.autograd.Function):
+    """The materialised scores ContrastMemory.forward returns, [B, K1] per side, with their backward."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, memory_v1, memory_v2, idx, T, n_data, Z, set_z, bad, update_y):
+        lib = _lib.load()
+        v1 = v1.contiguous() if isinstance(v1, torch.Tensor) else v1
+        v2 = v2.contiguous() if isinstance(v2, torch.Tensor) else v2
+        _crd_check(v1, v2, memory_v1, memory_v2, idx, n_data, Z, bad)
+        B, d = v1.shape
+        K1 = idx.shape[1]
+        dev = v1.device
+        out_v1 = torch.empty(B, K1, device=dev, dtype=torch.float32)
+        out_v2 = torch.empty(B, K1, device=dev, dtype=torch.float32)
+        ws, ws_bytes = _crd_workspace(lib, B, d, K1, dev)
+        with _timed("moma_crd_scores"):
+            check(lib.moma_crd_scores(_ptr(v1), _ptr(v2), _ptr(memory_v1), _ptr(memory_v2), _ptr(idx), B, d, K1, int(n_data),
+                                      float(T), _ptr(Z), int(bool(set_z)), _ptr(out_v1), _ptr(out_v2), _ptr(bad), _ptr(ws),
+                                      ws_bytes, _stream()), "moma_crd_scores")
+        # The reference's autograd keeps the gathered [B, K1, d] copy for the backward; here the backward gathers again, and the
+        # banks are rewritten in between at the rows `update_y` (crd_update_ behind this call).  So the pre-update value of those
+        # B rows is kept (B d floats per bank) and put back around the backward's gather.
+        ctx.save_for_backward(out_v1, out_v2)
+        ctx.banks, ctx.idx, ctx.bad, ctx.T, ctx.n_data = (memory_v1, memory_v2), idx, bad, T, n_data
+        ctx.rows_at = ctx.old_rows = None
+        if update_y is not None:
+            ctx.rows_at = update_y.clamp(0, int(n_data) - 1)        # (an index that is no row never becomes an address)
+            ctx.old_rows = (memory_v1.index_select(0, ctx.rows_at), memory_v2.index_select(0, ctx.rows_at))
+        return out_v1, out_v2
+
+    @staticmethod
+    def backward(ctx, dout_v1, dout_v2):
+        lib = _lib.load()
+        out_v1, out_v2 = ctx.saved_tensors
+        (memory_v1, memory_v2), idx, bad = ctx.banks, ctx.idx, ctx.bad
+        B, K1 = out_v1.shape
+        d = memory_v1.shape[1]
+        dev = out_v1.device
+        dout_v1 = dout_v1.contiguous(); dout_v2 = dout_v2.contiguous()
+        dv1 = torch.empty(B, d, device=dev, dtype=torch.float32)
+        dv2 = torch.empty(B, d, device=dev, dtype=torch.float32)
+        ws, ws_bytes = _crd_workspace(lib, B, d, K1, dev)
+        new_rows = None
+        if ctx.old_rows is not None:
+            with torch.no_grad():
+                new_rows = (memory_v1.index_select(0, ctx.rows_at), memory_v2.index_select(0, ctx.rows_at))
+                memory_v1.index_copy_(0, ctx.rows_at, ctx.old_rows[0]); memory_v2.index_copy_(0, ctx.rows_at, ctx.old_rows[1])
+        with _timed("moma_crd_scores_bwd"):
+            check(lib.moma_crd_scores_bwd(_ptr(dout_v1), _ptr(dout_v2), _ptr(out_v1), _ptr(out_v2), _ptr(memory_v1),
+                                          _ptr(memory_v2), _ptr(idx), B, d, K1, int(ctx.n_data), float(ctx.T), _ptr(dv1), _ptr(dv2),
+                                          _ptr(bad), _ptr(ws), ws_bytes, _stream()), "moma_crd_scores_bwd")
+        if new_rows is not None:
+            with torch.no_grad():
+                memory_v1.index_copy_(0, ctx.rows_at, new_rows[0]); memory_v2.index_copy_(0, ctx.rows_at, new_rows[1])
+        return dv1, dv2, None, None, None, None, None, None, None, None, None
+
+
+def crd_scores(v1, v2, memory_v1, memory_v2, idx, T: float, n_data: int, Z, set_z: bool, bad=None, update_y=None):
+    """-> (out_v1, out_v2), [B, K1] fp32: x of side 1 and of side 2.  The backward gathers the rows again from the banks;
+    update_y: the rows (int64 [B]) that crd_update_ rewrites between this call and its backward -- their pre-update value is kept
+    and stands in for them during the backward's gather."""
+    if bad is None and isinstance(v1, torch.Tensor) and v1.is_cuda:
+        bad = torch.zeros(1, device=v1.device, dtype=torch.int32)
+    return _CRDScores.apply(v1, v2, memory_v1, memory_v2, idx, float(T), int(n_data), Z, bool(set_z), bad, update_y)
+
+
+def crd_update_(memory_v1, memory_v2, v1, v2, y, momentum: float, bad=None) -> None:
+    """Momentum update of both banks in one launch (moma_crd_update); issue it behind the gather of the same step."""
+    lib = _lib.load()
+    _dev(memory_v1, "memory_v1"); _dev(memory_v2, "memory_v2"); _dev(v1, "v1"); _dev(v2, "v2"); _dev(y, "y", torch.int64)
+    if bad is None:
+        bad = torch.zeros(1, device=v1.device, dtype=torch.int32)
+    _dev(bad, "bad_index", torch.int32)
+    B, d = v1.shape
+    if v2.shape != v1.shape or memory_v1.shape != memory_v2.shape or memory_v1.shape[1] != d or y.shape != (B,):
+        raise ValueError(f"shape mismatch: v1 {tuple(v1.shape)} v2 {tuple(v2.shape)} banks {tuple(memory_v1.shape)} / "
+                         f"{tuple(memory_v2.shape)} y {tuple(y.shape)}")
+    with trace_range("moma_crd_update"):
+        check(lib.moma_crd_update(_ptr(memory_v1), _ptr(memory_v2), _ptr(v1), _ptr(v2), _ptr(y), B, d, memory_v1.shape[0],
+                                  float(momentum), _ptr(bad), _stream()), "moma_crd_update")

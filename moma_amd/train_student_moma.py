@@ -4,7 +4,9 @@ Keeps every flag and default of the reference's argument parser (train_student_m
 startup order of its main_worker (:227-392: seed -> probe batch -> student, teacher -> s_dim/t_dim probe ->
 build_mem -> broadcast_memory -> CMO -> SGD over the trainable list -> DDP(model_s)), so seeds, checkpoints
 and launch lines carry over.  What differs:
-  * only `--distill moma` (and `kd`) are built -- the other criteria are out of scope (SURVEY section 2);
+  * `--distill moma`, `kd` and `crd` (Contrastive Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on
+    the gather kernels of csrc/crd.hip; `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader,
+    `--n_data` to size the banks) are built -- the other comparison criteria are out of scope (SURVEY section 2);
   * real datasets need author-local folders; `--dataset synthetic` (default when the requested dataset is not
     available) feeds pre-generated batches of the same shape;
   * one process per GPU either through torchrun (RANK/LOCAL_RANK/WORLD_SIZE in the environment) or, as in the
@@ -36,7 +38,8 @@ import torch.optim as optim
 
 from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
-from .dataset.synthetic import SyntheticLoader
+from .crd import CRDLoss
+from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
 from .distiller_zoo import DistillKL
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
@@ -119,6 +122,9 @@ def build_parser():
                    help="student wrap at world size > 1: one flat gradient all-reduce per step (default) or stock DDP")
     p.add_argument("--no_fused", action="store_true", help="reference call sequence on materialised logits")
     p.add_argument("--steps_per_epoch", type=int, default=100, help="synthetic loader length")
+    p.add_argument("--n_data", type=int, default=None,
+                   help="--distill crd: samples in the training set = rows of the memory banks (default: steps_per_epoch * "
+                        "batch_size, the synthetic set; the reference hard-codes it per dataset)")
     p.add_argument("--num_heads", type=int, default=4)
     p.add_argument("--no_overlap_teacher", dest="overlap_teacher", action="store_false",
                    help="run the teacher / key side of the step on the main stream instead of a second HIP stream")
@@ -205,6 +211,17 @@ def build_training(opt, device):
         for name in ("atts", "atts_p", "atts_n", "atts_q", "atts_k", "atts_queue"):
             if hasattr(criterion_kd, name):
                 trainable_list.append(getattr(criterion_kd, name))
+    elif opt.distill == "crd":
+        # reference :305-322: both heads are built by the criterion and BOTH train (the teacher-side head too)
+        opt.s_dim = feat_s[-1].shape[1]
+        opt.t_dim = feat_t[-1].shape[1]
+        if getattr(opt, "n_data", None) is None:
+            opt.n_data = opt.steps_per_epoch * opt.batch_size
+        criterion_kd = CRDLoss(opt)                               # rand(n_data, feat_dim) x 2 drawn here
+        module_list.append(criterion_kd.embed_s)
+        module_list.append(criterion_kd.embed_t)
+        trainable_list.append(criterion_kd.embed_s)
+        trainable_list.append(criterion_kd.embed_t)
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
@@ -346,7 +363,11 @@ def main_worker(gpu, ngpus_per_node, opt):
 
     size = IMAGE_SIZE.get(opt.dataset, opt.image_size)
     seed = (opt.seed or 0) + opt.rank
-    train_loader = SyntheticLoader(opt.steps_per_epoch, opt.batch_size, size, opt.n_cls, seed, device)
+    if opt.distill == "crd":
+        train_loader = SyntheticSampleLoader(opt.steps_per_epoch, opt.batch_size, size, opt.n_cls, opt.nce_k, opt.mode, seed, device,
+                                             n_data=opt.n_data)
+    else:
+        train_loader = SyntheticLoader(opt.steps_per_epoch, opt.batch_size, size, opt.n_cls, seed, device)
     val_loader = SyntheticLoader(max(1, opt.steps_per_epoch // 10), opt.batch_size, size, opt.n_cls, seed + 1, device)
     is_main = (not opt.multiprocessing_distributed) or opt.rank % ngpus_per_node == 0
     if is_main:
@@ -369,6 +390,8 @@ def main_worker(gpu, ngpus_per_node, opt):
             qstate = (rs or {}).get("contrast") or ck.get("contrast")
             if qstate is not None:
                 contrast.load_state_dict(qstate)
+        if opt.distill == "crd" and rs is not None and rs.get("crd_banks") is not None:
+            criterion_list[2].contrast.load_state_dict(rs["crd_banks"])     # (the banks are per rank, as the reference's are)
         if rs is not None and rs.get("rng") is not None:
             _set_rng_state(rs["rng"], device)
         best_acc, best_f1, start_epoch = ck.get("best_acc", 0.0), ck.get("best_f1", 0.0), ck["epoch"] + 1
@@ -379,7 +402,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         print("==> training...")
         t1 = time.time()
         train_acc, train_loss = train_distill_moma(epoch, train_loader, module_list, criterion_list,
-                                                   trainer if opt.distill == "moma" else None, contrast, optimizer, opt)
+                                                   trainer if opt.distill in ("moma", "crd") else None, contrast, optimizer, opt)
         if device.type == "cuda":
             torch.cuda.synchronize()
         t2 = time.time()
@@ -426,6 +449,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         # resume only pairs files of the same epoch (_load_rank_state)
         os.makedirs(opt.save_folder, exist_ok=True)
         _atomic_save({"epoch": epoch, "contrast": contrast.state_dict() if contrast is not None else None,
+                      "crd_banks": criterion_list[2].contrast.state_dict() if opt.distill == "crd" else None,
                       "rng": _get_rng_state(device)}, _rank_state_path(opt.save_folder, opt.rank))
         if opt.multiprocessing_distributed and torch.distributed.is_initialized():
             torch.distributed.barrier()                         # no rank starts the next epoch before every file of this one exists
