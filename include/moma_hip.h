@@ -236,6 +236,39 @@ int moma_crd_update(float* memory_v1, float* memory_v2, const float* v1, const f
                     int64_t n_data, float momentum, int32_t* bad_index, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * AT   Attention Transfer (`--distill attention`, p = 2) on one pair of feature maps -- replaces Attention.at_loss
+ *      (distiller_zoo/AT.py: adaptive_avg_pool2d -> pow(2) -> mean(1) -> F.normalize -> (a_s - a_t).pow(2).mean()) and its
+ *      autograd backward.  For f [B,C,H,W] and an output grid oh x ow with H % oh == 0 and W % ow == 0 (window rh x rw =
+ *      H/oh x W/ow; 1 x 1 = no pooling):
+ *          pool(f)[b,c,y,x] = mean of the window      a[b, y ow + x] = (1/C) sum_c pool(f)[b,c,y,x]^2
+ *          ah = a / max(|a|_2, 1e-12) per batch row    loss = sum_b sum_i (ah_s - ah_t)[b,i]^2 / (B n),   n = oh ow
+ *          g_ah = +-2 (ah_s - ah_t) / (B n)            g_a = (g_ah - ah <ah, g_ah>) / |a|_2   (g_ah / 1e-12 under the clamp)
+ *          dF[b,c,Y,X] = g_loss * g_a[b, (Y/rh) ow + X/rw] * 2 / (C rh rw) * pool(f)[b,c,Y/rh,X/rw]
+ *      f, dF: MOMA_DT_F32 or MOMA_DT_BF16 (dtype), dense in MOMA_LAYOUT_NCHW or MOMA_LAYOUT_NHWC (channels_last memory
+ *      [B,H,W,C]; the shape arguments are the logical B, C, H, W either way), aligned to their element size -- 16-byte accesses
+ *      are used where the address and the contiguous extent (H W, or C) allow, element accesses otherwise.  Everything else
+ *      (a, norms, partials, loss, g_*, ah_*, g_loss) is fp32.  Accumulation over the channels in fp32; the pair in double.
+ *      No atomics: partial sums meet in a fixed order, results are bitwise reproducible.
+ *
+ * moma_at_map   a [B, oh ow] from one read of f.  workspace: moma_at_workspace_bytes() bytes (0 for most shapes: NULL is
+ *               accepted then), 16-byte aligned -- small NCHW maps are cut along the channels over several workgroups.
+ * moma_at_pair  both maps [B, n] -> norms [B, 2] (student, teacher), partials [B] (the row's sum of squared differences),
+ *               loss [1], and, each nullable, g_s / g_t [B, n] (d loss / d a_s, d loss / d a_t) and ah_s / ah_t [B, n].
+ *               A row with |a| = 0 gives ah = 0 and a finite g (no 0/0).
+ * moma_at_bwd   dF (dtype and layout of f) from one read of f and g_a [B, oh ow]; g_loss is a DEVICE scalar (the upstream
+ *               gradient of the loss, e.g. a GradScaler factor): nothing is read back to the host.
+ *      A grid that does not divide the map: MOMA_E_SHAPE (pool with other means first); unknown layout: MOMA_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_LAYOUT_NCHW = 0, MOMA_LAYOUT_NHWC = 1 };
+size_t moma_at_workspace_bytes(int B, int C, int H, int W, int oh, int ow, int dtype, int layout);
+int moma_at_map(const void* f, float* a, int B, int C, int H, int W, int oh, int ow, int dtype, int layout, void* workspace,
+                size_t workspace_bytes, moma_stream_t stream);
+int moma_at_pair(const float* a_s, const float* a_t, int B, int n, float* norms, float* partials, float* loss, float* g_s,
+                 float* g_t, float* ah_s, float* ah_t, moma_stream_t stream);
+int moma_at_bwd(const void* f, const float* g_a, const float* g_loss, void* dF, int B, int C, int H, int W, int oh, int ow,
+                int dtype, int layout, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1  batch-token multi-head attention -- replaces Attention.forward
  *     (MoMA/criterion_moco_att.py:153-167) and its autograd backward.
  *     x [N,d] -> qkv = x Wqkv^T + bqkv -> per head softmax(q k^T * hd^-1/2) v -> y = a Wproj^T + bproj.

@@ -640,4 +640,51 @@ int moma_crd_update(float* memory_v1, float* memory_v2, const float* v1, const f
     return hip_rc(launch_crd_update(memory_v1, memory_v2, v1, v2, y, B, d, n_data, momentum, bad_index, (hipStream_t)stream));
 }
 
+// ---- Attention Transfer ----------------------------------------------------------------------------------------------------
+static int at_check(int B, int C, int H, int W, int oh, int ow, int dtype, int layout) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0) return MOMA_E_SHAPE;
+    if (bad_dt(dtype)) return MOMA_E_DTYPE;
+    if (layout != MOMA_LAYOUT_NCHW && layout != MOMA_LAYOUT_NHWC) return MOMA_E_UNSUPPORTED;
+    if (H % oh != 0 || W % ow != 0) return MOMA_E_SHAPE;
+    if ((int64_t)oh * ow > INT32_MAX / 8) return MOMA_E_UNSUPPORTED;          // (pixel indices of one image are ints)
+    return MOMA_OK;
+}
+
+size_t moma_at_workspace_bytes(int B, int C, int H, int W, int oh, int ow, int dtype, int layout) {
+    if (at_check(B, C, H, W, oh, ow, dtype, layout) != MOMA_OK) return 0;
+    return at_workspace_bytes(B, C, H, W, oh, ow, layout);
+}
+
+int moma_at_map(const void* f, float* a, int B, int C, int H, int W, int oh, int ow, int dtype, int layout, void* workspace,
+                size_t workspace_bytes, moma_stream_t stream) {
+    if (!f || !a) return MOMA_E_NULL;
+    const int rc = at_check(B, C, H, W, oh, ow, dtype, layout);
+    if (rc != MOMA_OK) return rc;
+    const size_t need = at_workspace_bytes(B, C, H, W, oh, ow, layout);
+    if (need != 0 && !workspace) return MOMA_E_NULL;
+    if (workspace_bytes < need) return MOMA_E_WORKSPACE;
+    if (misaligned(f, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(a, 4) || (need != 0 && misaligned(workspace, 16))) return MOMA_E_ALIGN;
+    return hip_rc(launch_at_map(f, a, B, C, H, W, oh, ow, dtype, layout, workspace, (hipStream_t)stream));
+}
+
+int moma_at_pair(const float* a_s, const float* a_t, int B, int n, float* norms, float* partials, float* loss, float* g_s,
+                 float* g_t, float* ah_s, float* ah_t, moma_stream_t stream) {
+    if (!a_s || !a_t || !norms || !partials || !loss) return MOMA_E_NULL;
+    if (B <= 0 || n <= 0) return MOMA_E_SHAPE;
+    if (misaligned(a_s, 4) || misaligned(a_t, 4) || misaligned(norms, 4) || misaligned(partials, 4) || misaligned(loss, 4) ||
+        misaligned(g_s, 4) || misaligned(g_t, 4) || misaligned(ah_s, 4) || misaligned(ah_t, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_at_pair(a_s, a_t, B, n, norms, partials, loss, g_s, g_t, ah_s, ah_t, (hipStream_t)stream));
+}
+
+int moma_at_bwd(const void* f, const float* g_a, const float* g_loss, void* dF, int B, int C, int H, int W, int oh, int ow,
+                int dtype, int layout, moma_stream_t stream) {
+    if (!f || !g_a || !g_loss || !dF) return MOMA_E_NULL;
+    const int rc = at_check(B, C, H, W, oh, ow, dtype, layout);
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(f, eb) || misaligned(dF, eb) || misaligned(g_a, 4) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_at_bwd(f, g_a, g_loss, dF, B, C, H, W, oh, ow, dtype, layout, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -78,6 +78,53 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- typed vector access of the streaming kernels (se.hip, attention.hip): VEC elements of storage type T <-> fp32, one
+//      memory instruction of up to 16 bytes; the pointer must be aligned to VEC elements -----------------------------
+template <typename T, int VEC> struct PV;
+template <> struct PV<float, 4> {
+    static __device__ void ld(const float* p, float* v) { const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
+    static __device__ void st(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <> struct PV<float, 1> {
+    static __device__ void ld(const float* p, float* v) { v[0] = *p; }
+    static __device__ void st(float* p, const float* v) { *p = v[0]; }
+};
+template <> struct PV<bf16_raw, 8> {
+    static __device__ void ld(const bf16_raw* p, float* v) {
+        const uint4 a = *reinterpret_cast<const uint4*>(p);
+        const unsigned w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+    }
+    static __device__ void st(bf16_raw* p, const float* v) {
+        uint4 a;
+        a.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
+        a.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
+        a.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
+        a.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
+        *reinterpret_cast<uint4*>(p) = a;
+    }
+};
+template <> struct PV<bf16_raw, 4> {
+    static __device__ void ld(const bf16_raw* p, float* v) {
+        const uint2 a = *reinterpret_cast<const uint2*>(p);
+        v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
+        v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
+    }
+    static __device__ void st(bf16_raw* p, const float* v) {
+        uint2 a;
+        a.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
+        a.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
+        *reinterpret_cast<uint2*>(p) = a;
+    }
+};
+template <> struct PV<bf16_raw, 1> {
+    static __device__ void ld(const bf16_raw* p, float* v) { v[0] = bf16_to_f32(*p); }
+    static __device__ void st(bf16_raw* p, const float* v) { *p = f32_to_bf16(v[0]); }
+};
+template <typename T> __device__ __forceinline__ float ld1(const T* p) { float v; PV<T, 1>::ld(p, &v); return v; }
+template <typename T> __device__ __forceinline__ void st1(T* p, float v) { PV<T, 1>::st(p, &v); }
+
 // ---- generic batched GEMM:  C[m,n] (+)= alpha * sum_k A(m,k) * B(n,k) + bias[n] ----------------
 //   A(m,k) = transA ? A[k*lda + m] : A[m*lda + k]      (fp32)
 //   B(n,k) = transB ? B[k*ldb + n] : B[n*ldb + k]      (fp32 or bf16 storage)
@@ -137,6 +184,15 @@ hipError_t launch_crd_scores_bwd(const float* dout_v1, const float* dout_v2, con
                                  int64_t n_data, float T, float* dv1, float* dv2, int32_t* bad, void* ws, hipStream_t st);
 hipError_t launch_crd_update(float* memory_v1, float* memory_v2, const float* v1, const float* v2, const int64_t* y, int B, int d,
                              int64_t n_data, float momentum, int32_t* bad, hipStream_t st);
+
+// ---- attention.hip (Attention Transfer: spatial attention maps, the pair loss, the feature gradient) ----------------------
+size_t at_workspace_bytes(int B, int C, int H, int W, int oh, int ow, int layout);
+hipError_t launch_at_map(const void* f, float* a, int B, int C, int H, int W, int oh, int ow, int dtype, int layout, void* ws,
+                         hipStream_t st);
+hipError_t launch_at_pair(const float* a_s, const float* a_t, int B, int n, float* norms, float* partials, float* loss, float* g_s,
+                          float* g_t, float* ah_s, float* ah_t, hipStream_t st);
+hipError_t launch_at_bwd(const void* f, const float* g_a, const float* g_loss, void* dF, int B, int C, int H, int W, int oh, int ow,
+                         int dtype, int layout, hipStream_t st);
 
 // ---- infonce_fused.hip (one-pass flash-style kernel) ----------------------------------------------
 bool infonce_flash_supported(int B, int d, int K, int qdtype, int prec);

@@ -1,3 +1,4 @@
+from .AT import Attention
 from .KD import DistillKL
 
-__all__ = ["DistillKL"]
+__all__ = ["Attention", "DistillKL"]

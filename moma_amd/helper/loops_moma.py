@@ -13,6 +13,12 @@ on materialised logits.
 `--distill crd` (reference :246-262, :303-306): the loader yields (images, labels, index, contrast_idx); the KD term is
 CRDLoss(feat_s[-1], feat_t[-1], index, contrast_idx) with feat_t from the teacher's single no-grad forward.  No EMA, no
 Shuffle-BN, the teacher stays frozen; the step is eager (not served from HIP graphs).
+
+`--distill attention` (reference :287-292): the KD term is sum(Attention(feat_s[1:-1], feat_t[1:-1])) over the INTERMEDIATE feature
+maps of the student's forward and the teacher's single no-grad forward, handed to the criterion in the dtype and memory format the
+backbones produced (bf16 under `--amp bf16`, channels_last under `--channels_last`: csrc/attention.hip reads both natively).  No
+auxiliary module, no EMA, no ContrastTrainer; the teacher's forward is eager (its HIP-graph replay hands out the last feature only)
+and so is the step.
 """
 from __future__ import print_function
 
@@ -26,6 +32,7 @@ import torch.nn as nn
 from .util import AverageMeter, accuracy
 from ..learning.contrast_trainer import ContrastTrainer
 from ..learning.ddp import FlatDataParallel
+from .graphs import GraphedInference
 
 
 def _set_bn_train(m):
@@ -102,6 +109,10 @@ class MomaStep:
         """teacher forward #1 (:270-272), then the moma branch's no-grad part (:309-320, :327-329)."""
         opt, trainer, criterion_kd, model_t = self.opt, self.trainer, self.criterion_kd, self.model_t
         with self.autocast(), torch.no_grad():
+            if opt.distill == "attention":    # (:270-272, :287-292) every feature map, as autocast left it: an eager forward
+                ft, lt = teacher(images, is_feat=True, full_feats=True) if isinstance(teacher, GraphedInference) \
+                    else teacher(images, is_feat=True)
+                return lt.float(), [f.detach() for f in ft[1:-1]], None          # g_t rides in the key slot
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
             return lt.float(), ft[-1].float(), None
@@ -154,6 +165,8 @@ class MomaStep:
         f_s = None
         if opt.distill == "crd":
             f_s = feat_s[-1].float()                                                      # (:304)
+        if opt.distill == "attention":
+            out["g_s"] = list(feat_s[1:-1])                                               # (:289)
         if opt.distill == "moma":
             with self.autocast():
                 f_s = criterion_kd.embed_s(feat_s[-1])                                    # (:323-324)
@@ -213,6 +226,8 @@ class MomaStep:
         if opt.distill == "crd":                                                          # (:303-306) f_t rides in fw["k"]
             with self.autocast():
                 return criterion_kd(fw["f_s"], fw["k"], fw["index"], fw["contrast_idx"]).float()
+        if opt.distill == "attention":                                                    # (:287-292) g_t rides in fw["k"]
+            return sum(criterion_kd(fw["g_s"], fw["k"])).float()
         if opt.distill != "moma":
             raise NotImplementedError(opt.distill)
         f_s, k, all_k, qp = fw["f_s"], fw["k"], fw["all_k"], fw["qp"]

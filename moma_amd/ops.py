@@ -987,3 +987,102 @@ def crd_update_(memory_v1, memory_v2, v1, v2, y, momentum: float, bad=None) -> N
     with trace_range("moma_crd_update"):
         check(lib.moma_crd_update(_ptr(memory_v1), _ptr(memory_v2), _ptr(v1), _ptr(v2), _ptr(y), B, d, memory_v1.shape[0],
                                   float(momentum), _ptr(bad), _stream()), "moma_crd_update")
+
+
+# ------------------------------------------------------------------------------------------------
+# Attention Transfer: spatial attention maps of a feature pair   (distiller_zoo/AT.py, helper/loops_moma.py:287-292)
+# ------------------------------------------------------------------------------------------------
+def _at_side(f, name):
+    """-> (dense tensor, layout code): contiguous NCHW and channels_last are taken as they are, any other dense layout is copied"""
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() != 4 or f.dtype not in _DT_CODES:
+        raise TypeError(f"attention_loss: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+    if f.is_contiguous():
+        return f, _lib.LAYOUT_NCHW
+    if f.is_contiguous(memory_format=torch.channels_last):
+        return f, _lib.LAYOUT_NHWC
+    return f.contiguous(), _lib.LAYOUT_NCHW
+
+
+def _at_map(lib, f, layout, oh, ow):
+    B, Cc, H, W = f.shape
+    a = torch.empty(B, oh * ow, device=f.device, dtype=torch.float32)
+    dt = _DT_CODES[f.dtype]
+    n = lib.moma_at_workspace_bytes(B, Cc, H, W, oh, ow, dt, layout)
+    ws = torch.empty(n, device=f.device, dtype=torch.uint8) if n else None
+    check(lib.moma_at_map(_ptr(f), _ptr(a), B, Cc, H, W, oh, ow, dt, layout, _ptr(ws), n, _stream()), "moma_at_map")
+    return a
+
+
+class _AttentionLoss(torch.autograd.Function):
+    """at_map x 2 -> at_pair in the forward; at_bwd per side that needs a gradient in the backward."""
+
+    @staticmethod
+    def forward(ctx, f_s, f_t, oh, ow):
+        lib = _lib.load()
+        f_s, lay_s = _at_side(f_s, "f_s")
+        f_t, lay_t = _at_side(f_t, "f_t")
+        B = f_s.shape[0]
+        if f_t.shape[0] != B or f_s.shape[2] % oh or f_s.shape[3] % ow or f_t.shape[2] % oh or f_t.shape[3] % ow:
+            raise ValueError(f"attention_loss: f_s {tuple(f_s.shape)} and f_t {tuple(f_t.shape)} have no common {oh} x {ow} grid")
+        dev, n = f_s.device, oh * ow
+        need_s, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        with _timed("moma_at_fwd"):
+            a_s, a_t = _at_map(lib, f_s, lay_s, oh, ow), _at_map(lib, f_t, lay_t, oh, ow)
+            norms = torch.empty(B, 2, device=dev, dtype=torch.float32)
+            partials = torch.empty(B, device=dev, dtype=torch.float32)
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            g_s = torch.empty(B, n, device=dev, dtype=torch.float32) if need_s else None
+            g_t = torch.empty(B, n, device=dev, dtype=torch.float32) if need_t else None
+            check(lib.moma_at_pair(_ptr(a_s), _ptr(a_t), B, n, _ptr(norms), _ptr(partials), _ptr(loss), _ptr(g_s), _ptr(g_t),
+                                   _ptr(None), _ptr(None), _stream()), "moma_at_pair")
+        ctx.save_for_backward(*[t for t, need in ((f_s, need_s), (g_s, need_s), (f_t, need_t), (g_t, need_t)) if need])
+        ctx.sides = (need_s, need_t)
+        ctx.grid, ctx.layouts = (oh, ow), (lay_s, lay_t)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        saved = list(ctx.saved_tensors)
+        oh, ow = ctx.grid
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        out = [None, None]
+        with _timed("moma_at_bwd"):
+            for side, need in enumerate(ctx.sides):
+                if not need:
+                    continue
+                f, g_a = saved.pop(0), saved.pop(0)
+                B, Cc, H, W = f.shape
+                dF = torch.empty_like(f)               # (same dtype, same strides: NCHW or channels_last)
+                check(lib.moma_at_bwd(_ptr(f), _ptr(g_a), _ptr(g), _ptr(dF), B, Cc, H, W, oh, ow, _DT_CODES[f.dtype],
+                                      ctx.layouts[side], _stream()), "moma_at_bwd")
+                out[side] = dF
+        return out[0], out[1], None, None
+
+
+def attention_loss(f_s, f_t) -> torch.Tensor:
+    """Attention Transfer loss (p = 2) of one feature pair, f_s [B,Cs,Hs,Ws] and f_t [B,Ct,Ht,Wt] (float32 or bfloat16, contiguous
+    or channels_last, independently per side) -> scalar float32:  mean((ah_s - ah_t)^2) with a = mean_c f^2, ah = a / max(|a|, 1e-12).
+    Heights that differ: the larger map is average-pooled to (h, h), h = min(Hs, Ht) -- inside the kernels when h divides its H and
+    W, with stock adaptive_avg_pool2d in front of them otherwise.  Gradients flow to whichever side requires one."""
+    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
+        _dev(t, nm, dtype=None, contiguous=False)
+        if t.dim() != 4:
+            raise ValueError(f"attention_loss: {nm} must be [B,C,H,W], got {tuple(t.shape)}")
+    Hs, Ht = f_s.shape[2], f_t.shape[2]
+    if Hs == Ht:
+        oh, ow = Hs, f_s.shape[3]
+        if f_t.shape[3] != ow:
+            raise ValueError(f"attention_loss: equal heights but widths {ow} and {f_t.shape[3]}: the maps have no common grid")
+    else:
+        oh = ow = min(Hs, Ht)
+        if Hs > Ht and (Hs % oh or f_s.shape[3] % ow):
+            f_s = torch.nn.functional.adaptive_avg_pool2d(f_s, (oh, ow))
+        elif Ht > Hs and (Ht % oh or f_t.shape[3] % ow):
+            f_t = torch.nn.functional.adaptive_avg_pool2d(f_t, (oh, ow))
+        small = f_t if Hs > Ht else f_s
+        if small.shape[3] != ow:
+            raise ValueError(f"attention_loss: the smaller map {tuple(small.shape)} is not square: no common {oh} x {ow} grid")
+    return _AttentionLoss.apply(f_s, f_t, int(oh), int(ow))

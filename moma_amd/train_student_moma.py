@@ -4,9 +4,11 @@ Keeps every flag and default of the reference's argument parser (train_student_m
 startup order of its main_worker (:227-392: seed -> probe batch -> student, teacher -> s_dim/t_dim probe ->
 build_mem -> broadcast_memory -> CMO -> SGD over the trainable list -> DDP(model_s)), so seeds, checkpoints
 and launch lines carry over.  What differs:
-  * `--distill moma`, `kd` and `crd` (Contrastive Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on
-    the gather kernels of csrc/crd.hip; `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader,
-    `--n_data` to size the banks) are built -- the other comparison criteria are out of scope (SURVEY section 2);
+  * `--distill moma`, `kd`, `attention` (Attention Transfer over the intermediate feature maps: distiller_zoo/AT.py on the kernels of
+    csrc/attention.hip; the reference's launch line is `--distill attention -c 1 -d 1 -b 1000`) and `crd` (Contrastive
+    Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
+    `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
+    built -- the other comparison criteria are out of scope (SURVEY section 2);
   * real datasets need author-local folders; `--dataset synthetic` (default when the requested dataset is not
     available) feeds pre-generated batches of the same shape;
   * one process per GPU either through torchrun (RANK/LOCAL_RANK/WORLD_SIZE in the environment) or, as in the
@@ -40,7 +42,7 @@ from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
-from .distiller_zoo import DistillKL
+from .distiller_zoo import Attention, DistillKL
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
 from .learning.contrast_trainer import ContrastTrainer
@@ -222,6 +224,8 @@ def build_training(opt, device):
         module_list.append(criterion_kd.embed_t)
         trainable_list.append(criterion_kd.embed_s)
         trainable_list.append(criterion_kd.embed_t)
+    elif opt.distill == "attention":
+        criterion_kd = Attention()                                # reference :298-299: p = 2, nothing to train, no memory
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
