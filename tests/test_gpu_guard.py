@@ -249,3 +249,58 @@ def test_backbone_helper_writes_stay_inside(guard, shape, dtype):
         y.float().sum().backward()
         guard.check(f"bn backward {shape} {dtype} training={training}")
         assert torch.isfinite(x.grad.float()).all()
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+@pytest.mark.parametrize("B,d,K", [(80, 128, 100), (33, 50, 257)])
+def test_logits_gradients_to_k_and_queue_stay_inside(guard, prec, B, d, K, monkeypatch):
+    """materialised logits with q, k and an fp32 queue all requiring grad: dk and dqueue of moma_infonce_logits_bwd_kq next to the logits
+    and dq -- at (80, 128, 100) under bf16 dqueue comes from linear_ksplit_kernel<true,true> with ragged M = K = 100 (clamped tail rows,
+    masked store); at (33, 50, 257) every operand of every product goes through the element loads of the tiled kernel"""
+    from moma_amd import ops
+    rng = np.random.default_rng(B * 5 + d + K)
+    q0 = _rand(rng, B, d, scale=1 / np.sqrt(d))
+    k0 = _rand(rng, B, d, scale=1 / np.sqrt(d))
+    queue0 = torch.nn.functional.normalize(_rand(rng, K, d))
+    w0 = _rand(rng, B, K + 1)
+
+    def run(q, k, queue, w):
+        q, k, queue = q.requires_grad_(True), k.requires_grad_(True), queue.requires_grad_(True)
+        logits = ops.infonce_logits(q, k, queue, 0.15, prec)
+        (logits * w).sum().backward()
+        return [logits.detach(), q.grad, k.grad, queue.grad]
+
+    with monkeypatch.context() as m:
+        m.setattr(ops, "torch", torch)
+        ref = run(q0.clone(), k0.clone(), queue0.clone(), w0)
+    got = run(_in(guard, q0), _in(guard, k0), _in(guard, queue0), _in(guard, w0))
+    guard.check(f"logits dk/dqueue {prec} {(B, d, K)}")
+    for a, b in zip(ref, got):
+        assert torch.isfinite(b).all() and torch.equal(a, b)
+
+
+@pytest.mark.parametrize("N,d,H", [(80, 192, 8), (37, 50, 5)])
+def test_staged_mha_under_bf16_writes_stay_inside(guard, N, d, H, monkeypatch):
+    """head dims that are no multiple of 16 keep the bf16 policy on the staged path: at (80, 192, 8) the linear_ksplit variants
+    (ragged 32-row tiles, batched per head, column sum fused into dW), at (37, 50, 5) element loads throughout and colsum_kernel"""
+    from moma_amd import ops, _lib
+    assert _lib.load().moma_mha_saved_state(N, d, H, ops.PREC_BF16) == _lib.MHA_SAVE_PROBS
+    rng = np.random.default_rng(N + d + H)
+    x0 = _rand(rng, N, d, scale=1 / np.sqrt(d))
+    ws0 = [_rand(rng, *s, scale=1 / np.sqrt(d)) for s in ((3 * d, d), (3 * d,), (d, d), (d,))]
+    dy0 = _rand(rng, N, d)
+
+    def run(x, ws, dy):
+        x = x.requires_grad_(True)
+        ws = [w.requires_grad_(True) for w in ws]
+        y = ops.mha(x, *ws, H, "bf16")
+        (y * dy).sum().backward()
+        return [y.detach(), x.grad] + [w.grad for w in ws]
+
+    with monkeypatch.context() as m:
+        m.setattr(ops, "torch", torch)
+        ref = run(x0.clone(), [w.clone() for w in ws0], dy0)
+    got = run(_in(guard, x0), [_in(guard, w) for w in ws0], _in(guard, dy0))
+    guard.check(f"staged K1 bf16 {(N, d, H)}")
+    for a, b in zip(ref, got):
+        assert torch.isfinite(b).all() and torch.equal(a, b)
