@@ -1,6 +1,6 @@
 // K1 fast path: batch-token multi-head attention (MoMA/criterion_moco_att.py:153-167) under the bf16 policy for head dims that
 // are multiples of 16: up to 128 -- every `--head mlp` configuration -- at any N, wider heads (`--head None`: 1280 / 4 = 320) at
-// N <= 256.  The problem is tiny (N = 256 tokens, d = 512: 0.67 GFLOP
+// N <= 1024.  The problem is tiny (N = 256 tokens, d = 512: 0.67 GFLOP
 // per module forward) and therefore bound by launches and by the bytes each compute unit can pull from L2 (60-70 GB/s per CU),
 // not by the matrix pipe.  The path is built around that:
 //   * every operand a kernel reads more than once per launch is stored as bf16 (weights: a pack refreshed when the optimizer
