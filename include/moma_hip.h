@@ -359,6 +359,16 @@ int moma_bn_bwd(const void* x, const void* dout, const float* gamma, const float
                 const float* save_mean, const float* save_invstd, void* dx, float* dgamma, float* dbeta,
                 void* workspace, size_t workspace_bytes, int N, int C, int HW, int dtype, int act,
                 int training, const void* dplane_mean, moma_stream_t stream);
+/*     The forward without its apply pass, for a consumer that applies the normalisation itself while it reads x
+ *     (the _pre entry points of the depthwise convolution below): the statistics, the running-statistics update,
+ *     save_mean / save_invstd and scale_shift [C][2] fp32 (caller-owned) with
+ *       act(BN(x))[n,c,:] = act(x[n,c,:] * scale_shift[c][0] + scale_shift[c][1]),
+ *     bit-identical to what the forward call computes for the same x (training == 0: from the running statistics).
+ *     Same workspace as the forward call; moma_bn_bwd takes x and the saved statistics as after a forward call. */
+int moma_bn_prepare(const void* x, const float* gamma, const float* beta, float* running_mean,
+                    float* running_var, float* save_mean, float* save_invstd, float* scale_shift,
+                    void* workspace, size_t workspace_bytes, int N, int C, int HW, int dtype, int training,
+                    float momentum, float eps, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * DW  depthwise convolution (groups == channels) on NCHW activations -- the MBConv `_depthwise_conv`
@@ -378,6 +388,18 @@ int moma_dwconv_bwd_data(const void* dy, const float* w, void* dx, int N, int C,
 int moma_dwconv_bwd_weight(const void* x, const void* dy, float* dw, void* workspace,
                            size_t workspace_bytes, int N, int C, int H, int W, int OH, int OW, int K,
                            int stride, int pad_top, int pad_left, int dtype, moma_stream_t stream);
+/*     The same two calls on a = act(BN(x)) without a materialised a: x is the BatchNorm's input and scale_shift
+ *     [C][2] fp32 comes from moma_bn_prepare; every element is normalised, activated (act: MOMA_ACT_*) and rounded
+ *     to the storage dtype as it is read, the zero padding is that of a.  Results are bit-identical to
+ *     moma_bn_fwd followed by the plain call.  (The gradient w.r.t. a is moma_dwconv_bwd_data as it is; moma_bn_bwd
+ *     then turns it into the gradient w.r.t. x.)  An act outside MOMA_ACT_* is answered with MOMA_E_DTYPE, as by the BN calls. */
+int moma_dwconv_fwd_pre(const void* x, const float* w, void* y, int N, int C, int H, int W, int OH, int OW,
+                        int K, int stride, int pad_top, int pad_left, int dtype, const float* scale_shift,
+                        int act, moma_stream_t stream);
+int moma_dwconv_bwd_weight_pre(const void* x, const void* dy, float* dw, void* workspace,
+                               size_t workspace_bytes, int N, int C, int H, int W, int OH, int OW, int K,
+                               int stride, int pad_top, int pad_left, int dtype, const float* scale_shift,
+                               int act, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SE  squeeze-excite helpers on NCHW activations (models/efficientnet_pytorch/model.py:104-110):

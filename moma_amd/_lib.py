@@ -66,12 +66,15 @@ SIGNATURES = {
     "moma_dwconv_fwd": (_i, [_p, _p, _p] + [_i] * 11 + [_p]),
     "moma_dwconv_bwd_data": (_i, [_p, _p, _p] + [_i] * 11 + [_p]),
     "moma_dwconv_bwd_weight": (_i, [_p, _p, _p, _p, _z] + [_i] * 11 + [_p]),
+    "moma_dwconv_fwd_pre": (_i, [_p, _p, _p] + [_i] * 11 + [_p, _i, _p]),
+    "moma_dwconv_bwd_weight_pre": (_i, [_p, _p, _p, _p, _z] + [_i] * 11 + [_p, _i, _p]),
     "moma_plane_mean": (_i, [_p, _p, _i, _i, _i, _p]),
     "moma_se_gate_fwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "moma_se_gate_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "moma_bn_workspace_bytes": (_z, [_i]),
     "moma_bn_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p]),
     "moma_bn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "moma_bn_prepare": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _f, _p]),
     "moma_mha_bwd_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "moma_mha_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
 }

@@ -27,6 +27,13 @@ _BN_MODE = os.environ.get("MOMA_BN", "hip")
 #   squeeze-excite        : MOMA_SE=hip (default) = per-plane mean and the sigmoid gate (one-pass backward) on the
 #                           library's kernels (se.hip); "aten" = adaptive_avg_pool2d / sigmoid / mul.
 _SE_MODE = os.environ.get("MOMA_SE", "hip")
+#   _bn0 + SiLU -> depthwise: MOMA_BNDW=1 (default) = where both of the above take their hip paths and no gradient is recorded
+#                           (the teacher's passes, evaluation), the expanded tensor's BN0 + SiLU is applied inside the depthwise
+#                           kernels as they read it (ops.bn_act_dwconv: the activation in between is neither written nor read
+#                           back, bit-identical results); "grad" = in recorded forwards too (measured a loss there: the
+#                           prologue inside backward-weight costs more than the apply pass it removes);
+#                           0 = the two calls everywhere.
+_BNDW_FUSE = os.environ.get("MOMA_BNDW", "1")
 
 # (repeats, kernel, stride, expand, cin, cout, se_ratio) -- EfficientNet-B0 stage table
 _B0_STAGES = [
@@ -87,6 +94,11 @@ class _CachedCast(torch.autograd.Function):
 _WCACHE = os.environ.get("MOMA_WCACHE", "1") == "1"
 
 
+def _same_pad(ih, iw, kh, kw, sh, sw):
+    """total (rows, columns) of TensorFlow 'SAME' padding for an ih x iw input"""
+    return (max((math.ceil(ih / sh) - 1) * sh + kh - ih, 0), max((math.ceil(iw / sw) - 1) * sw + kw - iw, 0))
+
+
 class SamePadConv2d(nn.Conv2d):
     """Conv2d with TensorFlow 'SAME' padding computed from the input size at call time."""
 
@@ -106,13 +118,15 @@ class SamePadConv2d(nn.Conv2d):
             return w, b
         return self.weight, self.bias
 
+    def _is_depthwise(self):
+        return self.groups > 1 and self.groups == self.in_channels == self.out_channels and self.bias is None
+
     def forward(self, x):
         ih, iw = x.shape[-2:]
         kh, kw = self.kernel_size
         sh, sw = self.stride
-        ph = max((math.ceil(ih / sh) - 1) * sh + kh - ih, 0)
-        pw = max((math.ceil(iw / sw) - 1) * sw + kw - iw, 0)
-        depthwise = self.groups > 1 and self.groups == self.in_channels == self.out_channels and self.bias is None
+        ph, pw = _same_pad(ih, iw, kh, kw, sh, sw)
+        depthwise = self._is_depthwise()
         if depthwise and x.is_cuda and _DW_MODE == "hip" and kh == kw and sh == sw and self.dilation == (1, 1):
             from .. import ops
             if ops.dwconv_supported(kh, sh):
@@ -198,11 +212,43 @@ class MBConvBlock(nn.Module):
         self._project_conv = SamePadConv2d(mid, cout, 1, bias=False)
         self._bn2 = BatchNorm2d(cout, momentum=_BN_MOM, eps=_BN_EPS)
 
+    def _bn0_depthwise(self, e):
+        """_depthwise_conv(_bn0(e) + SiLU) in one op (ops.bn_act_dwconv) under exactly the conditions under which BOTH modules
+        would take their hip paths; None otherwise.  The mode switches are read at call time."""
+        bn, dw = self._bn0, self._depthwise_conv
+        if not (_BNDW_FUSE in ("1", "grad") and _BN_MODE == "hip" and _DW_MODE == "hip" and e.is_cuda and bn.momentum is not None):
+            return None
+        if _BNDW_FUSE != "grad" and torch.is_grad_enabled() and (
+                e.requires_grad or dw.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
+            return None
+        (kh, kw), (sh, sw) = dw.kernel_size, dw.stride
+        if not (dw._is_depthwise() and kh == kw and sh == sw and dw.dilation == (1, 1)) or e.dtype not in (torch.float32, torch.bfloat16):
+            return None
+        # (the depthwise module casts its input to the autocast dtype: only where that cast is none, the pair is one op)
+        if torch.is_autocast_enabled() and e.dtype != torch.get_autocast_dtype("cuda"):
+            return None
+        from .. import ops
+        if not ops.dwconv_supported(kh, sh):
+            return None
+        use_batch = bn.training or bn.running_mean is None
+        if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn._nbt_pending += 1
+        ih, iw = e.shape[-2:]
+        ph, pw = _same_pad(ih, iw, kh, kw, sh, sw)
+        return ops.bn_act_dwconv(e, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch, bn.momentum, bn.eps, "silu",
+                                 dw.weight, sh, ph // 2, pw // 2, math.ceil(ih / sh), math.ceil(iw / sw))
+
     def forward(self, x, drop_connect_rate=None):
         inp = x
+        d = None
         if self.expand != 1:
-            x = self._bn0(self._expand_conv(x), act="silu")
-        x, pooled = self._bn1(self._depthwise_conv(x), act="silu", want_mean=True)      # squeeze fused into the BN pass
+            x = self._expand_conv(x)
+            d = self._bn0_depthwise(x)
+            if d is None:
+                x = self._bn0(x, act="silu")
+        if d is None:
+            d = self._depthwise_conv(x)
+        x, pooled = self._bn1(d, act="silu", want_mean=True)      # squeeze fused into the BN pass
         s = self._se_expand(F.silu(self._se_reduce(pooled)))
         if _SE_MODE == "hip" and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16):
             from .. import ops

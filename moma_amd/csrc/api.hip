@@ -493,6 +493,17 @@ int moma_bn_fwd(const void* x, void* out, const float* gamma, const float* beta,
                                 (float*)workspace, N, C, HW, dtype, act, training, momentum, eps, plane_mean, (hipStream_t)stream));
 }
 
+int moma_bn_prepare(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                    float* save_mean, float* save_invstd, float* scale_shift, void* workspace, size_t workspace_bytes, int N,
+                    int C, int HW, int dtype, int training, float momentum, float eps, moma_stream_t stream) {
+    if (!x || !save_mean || !save_invstd || !scale_shift) return MOMA_E_NULL;
+    if (!training && (!running_mean || !running_var)) return MOMA_E_NULL;
+    const int rc = bn_check(N, C, HW, dtype, MOMA_ACT_NONE, workspace, workspace_bytes);
+    if (rc != MOMA_OK) return rc;
+    return hip_rc(launch_bn_prepare(x, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale_shift,
+                                    (float*)workspace, N, C, HW, dtype, training, momentum, eps, (hipStream_t)stream));
+}
+
 int moma_bn_bwd(const void* x, const void* dout, const float* gamma, const float* beta, const float* save_mean,
                 const float* save_invstd, void* dx, float* dgamma, float* dbeta, void* workspace,
                 size_t workspace_bytes, int N, int C, int HW, int dtype, int act, int training,
@@ -523,7 +534,20 @@ int moma_dwconv_fwd(const void* x, const float* w, void* y, int N, int C, int H,
     if (!x || !w || !y) return MOMA_E_NULL;
     const int rc = dw_check(N, C, H, W, OH, OW, K, stride, pad_top, pad_left, dtype);
     if (rc != MOMA_OK) return rc;
-    return hip_rc(launch_dw_fwd(x, w, y, N, C, H, W, OH, OW, K, stride, pad_top, pad_left, dtype, (hipStream_t)stream));
+    return hip_rc(launch_dw_fwd(x, w, y, N, C, H, W, OH, OW, K, stride, pad_top, pad_left, dtype, nullptr, MOMA_ACT_NONE,
+                                (hipStream_t)stream));
+}
+
+static bool bad_act(int act) { return act != MOMA_ACT_NONE && act != MOMA_ACT_SILU && act != MOMA_ACT_RELU; }
+
+int moma_dwconv_fwd_pre(const void* x, const float* w, void* y, int N, int C, int H, int W, int OH, int OW, int K, int stride,
+                        int pad_top, int pad_left, int dtype, const float* scale_shift, int act, moma_stream_t stream) {
+    if (!x || !w || !y || !scale_shift) return MOMA_E_NULL;
+    const int rc = dw_check(N, C, H, W, OH, OW, K, stride, pad_top, pad_left, dtype);
+    if (rc != MOMA_OK) return rc;
+    if (bad_act(act)) return MOMA_E_DTYPE;
+    return hip_rc(launch_dw_fwd(x, w, y, N, C, H, W, OH, OW, K, stride, pad_top, pad_left, dtype, scale_shift, act,
+                                (hipStream_t)stream));
 }
 
 int moma_dwconv_bwd_data(const void* dy, const float* w, void* dx, int N, int C, int H, int W, int OH, int OW, int K,
@@ -542,7 +566,19 @@ int moma_dwconv_bwd_weight(const void* x, const void* dy, float* dw, void* works
     if (rc != MOMA_OK) return rc;
     if (workspace_bytes < moma_dwconv_workspace_bytes(C, K)) return MOMA_E_WORKSPACE;
     return hip_rc(launch_dw_bwd_weight(x, dy, dw, (float*)workspace, workspace_bytes / sizeof(float), N, C, H, W, OH, OW, K,
-                                       stride, pad_top, pad_left, dtype, (hipStream_t)stream));
+                                       stride, pad_top, pad_left, dtype, nullptr, MOMA_ACT_NONE, (hipStream_t)stream));
+}
+
+int moma_dwconv_bwd_weight_pre(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int C,
+                               int H, int W, int OH, int OW, int K, int stride, int pad_top, int pad_left, int dtype,
+                               const float* scale_shift, int act, moma_stream_t stream) {
+    if (!x || !dy || !dw || !workspace || !scale_shift) return MOMA_E_NULL;
+    const int rc = dw_check(N, C, H, W, OH, OW, K, stride, pad_top, pad_left, dtype);
+    if (rc != MOMA_OK) return rc;
+    if (bad_act(act)) return MOMA_E_DTYPE;
+    if (workspace_bytes < moma_dwconv_workspace_bytes(C, K)) return MOMA_E_WORKSPACE;
+    return hip_rc(launch_dw_bwd_weight(x, dy, dw, (float*)workspace, workspace_bytes / sizeof(float), N, C, H, W, OH, OW, K,
+                                       stride, pad_top, pad_left, dtype, scale_shift, act, (hipStream_t)stream));
 }
 
 static int se_check(int NC, int HW, int dtype) {

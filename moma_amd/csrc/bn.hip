@@ -3,6 +3,7 @@
 // `_swish(_bn0(...))`, `_swish(_bn1(...))`, `_bn2(...)`; torch semantics of nn.BatchNorm2d in training and eval
 // mode incl. the running-statistics update).  Pure HBM streaming work:
 //   forward  train: read x (statistics), read x again + write out          = 3 passes over the activation
+//                   (1 pass where the consumer applies scale / shift itself: launch_bn_prepare + dwconv.hip's prologue)
 //   backward      : read x, dout (reductions), read x, dout + write dx     = 5 passes
 // (unfused torch: BN forward + activation forward = 5 passes, backward 8, and the pre-activation tensor is kept).
 // The backward recomputes the pre-activation y = xhat*gamma + beta in fp32 from x and the saved statistics, so
@@ -85,11 +86,7 @@ struct VecIO<bf16_raw, VEC> {
     }
 };
 
-__device__ __forceinline__ float act_fwd(float y, int act) {
-    if (act == MOMA_ACT_SILU) return y / (1.f + __expf(-y));
-    if (act == MOMA_ACT_RELU) return fmaxf(y, 0.f);
-    return y;
-}
+// (act_fwd: common.hpp)
 // d act(y) / dy
 __device__ __forceinline__ float act_grad(float y, int act) {
     if (act == MOMA_ACT_SILU) {
@@ -370,15 +367,13 @@ unsigned apply_grid(size_t nvec) {
     return (unsigned)g;
 }
 
+// statistics (training) + finalize: save_mean / save_invstd / scale_shift [C][2] and the running-statistics update.
+// `partial` = the workspace behind its first 2*C floats ([C][S][3]); `vec` = the vector width of the caller's walk over x.
 template <typename T>
-hipError_t bn_fwd_t(const T* x, T* out, const float* gamma, const float* beta, float* rm, float* rv, float* save_mean,
-                    float* save_invstd, float* ws, int N, int C, int HW, int act, int training, float momentum,
-                    float eps, T* pmean, hipStream_t st) {
-    const int vec = pick_vec(HW, sizeof(T), x, out, nullptr);
+void bn_prepare_t(const T* x, const float* gamma, const float* beta, float* rm, float* rv, float* save_mean, float* save_invstd,
+                  float* scale_shift, float* partial, int N, int C, int HW, int vec, int training, float momentum, float eps,
+                  hipStream_t st) {
     const int S = training ? pick_splits(N, C, HW, vec) : 1;
-    float* scale_shift = ws;                   // [C][2]
-    float* partial = ws + 2 * (size_t)C;       // [C][S][3]
-    const size_t nvec = (size_t)N * C * HW / vec;
     if (training) {
         dim3 grid(S, C);
         if (vec == 8) hipLaunchKernelGGL((bn_stats_kernel<T, 8>), grid, dim3(BN_THREADS), 0, st, x, partial, N, C, HW);
@@ -387,6 +382,18 @@ hipError_t bn_fwd_t(const T* x, T* out, const float* gamma, const float* beta, f
     }
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, partial, S, gamma, beta, rm, rv,
                        save_mean, save_invstd, scale_shift, C, training, momentum, eps);
+}
+
+template <typename T>
+hipError_t bn_fwd_t(const T* x, T* out, const float* gamma, const float* beta, float* rm, float* rv, float* save_mean,
+                    float* save_invstd, float* ws, int N, int C, int HW, int act, int training, float momentum,
+                    float eps, T* pmean, hipStream_t st) {
+    const int vec = pick_vec(HW, sizeof(T), x, out, nullptr);
+    float* scale_shift = ws;                   // [C][2]
+    float* partial = ws + 2 * (size_t)C;       // [C][S][3]
+    const size_t nvec = (size_t)N * C * HW / vec;
+    bn_prepare_t<T>(x, gamma, beta, rm, rv, save_mean, save_invstd, scale_shift, partial, N, C, HW, vec, training, momentum, eps,
+                    st);
     if (pmean) {
         long gp = ((long)N * C + BN_THREADS / 64 - 1) / (BN_THREADS / 64);
         if (gp > 256 * 32) gp = 256 * 32;
@@ -438,6 +445,20 @@ hipError_t launch_bn_fwd(const void* x, void* out, const float* gamma, const flo
                                   C, HW, act, training, momentum, eps, (bf16_raw*)plane_mean, st);
     return bn_fwd_t<float>((const float*)x, (float*)out, gamma, beta, rm, rv, save_mean, save_invstd, ws, N, C, HW, act,
                            training, momentum, eps, (float*)plane_mean, st);
+}
+// the forward without its apply pass: what launch_bn_fwd computes ahead of it, for a consumer that applies scale / shift itself
+// (same kernels, split count and merge order: x's own alignment picks the vector width, as it does next to an aligned `out`)
+hipError_t launch_bn_prepare(const void* x, const float* gamma, const float* beta, float* rm, float* rv, float* save_mean,
+                             float* save_invstd, float* scale_shift, float* ws, int N, int C, int HW, int dtype, int training,
+                             float momentum, float eps, hipStream_t st) {
+    float* partial = ws + 2 * (size_t)C;
+    if (dtype == MOMA_DT_BF16)
+        bn_prepare_t<bf16_raw>((const bf16_raw*)x, gamma, beta, rm, rv, save_mean, save_invstd, scale_shift, partial, N, C, HW,
+                               pick_vec(HW, sizeof(bf16_raw), x, nullptr, nullptr), training, momentum, eps, st);
+    else
+        bn_prepare_t<float>((const float*)x, gamma, beta, rm, rv, save_mean, save_invstd, scale_shift, partial, N, C, HW,
+                            pick_vec(HW, sizeof(float), x, nullptr, nullptr), training, momentum, eps, st);
+    return hipGetLastError();
 }
 hipError_t launch_bn_bwd(const void* x, const void* dout, const float* gamma, const float* beta, const float* save_mean,
                          const float* save_invstd, void* dx, float* dgamma, float* dbeta, float* ws, int N, int C, int HW,

@@ -23,6 +23,14 @@ __device__ __forceinline__ bf16_raw f32_to_bf16(float f) {
     return *reinterpret_cast<bf16_raw*>(&b);
 }
 
+// the activation that follows a BatchNorm (MOMA_ACT_*): THE formula of bn.hip's apply kernels and of the depthwise kernels'
+// pre-activation prologue (dwconv.hip), which must reproduce the former bit for bit
+__device__ __forceinline__ float act_fwd(float y, int act) {
+    if (act == MOMA_ACT_SILU) return y / (1.f + __expf(-y));
+    if (act == MOMA_ACT_RELU) return fmaxf(y, 0.f);
+    return y;
+}
+
 // two floats -> one word of two bf16 (lo in bits 0..15), round to nearest even: ONE v_cvt_pk_bf16_f32.  Written as
 // `f32_to_bf16(lo) | f32_to_bf16(hi) << 16` hipcc pairs the conversions of a 16-byte store the wrong way round (values 0,2 / 1,3)
 // and puts the words together again with v_and / v_lshl / 2 x v_or_sdwa: 20 VALU instructions per store instead of 12 -- seen
@@ -239,6 +247,9 @@ size_t bn_workspace_floats(int C);
 hipError_t launch_bn_fwd(const void* x, void* out, const float* gamma, const float* beta, float* rm, float* rv,
                          float* save_mean, float* save_invstd, float* ws, int N, int C, int HW, int dtype, int act,
                          int training, float momentum, float eps, void* plane_mean, hipStream_t st);
+hipError_t launch_bn_prepare(const void* x, const float* gamma, const float* beta, float* rm, float* rv, float* save_mean,
+                             float* save_invstd, float* scale_shift, float* ws, int N, int C, int HW, int dtype, int training,
+                             float momentum, float eps, hipStream_t st);
 hipError_t launch_bn_bwd(const void* x, const void* dout, const float* gamma, const float* beta, const float* save_mean,
                          const float* save_invstd, void* dx, float* dgamma, float* dbeta, float* ws, int N, int C, int HW,
                          int dtype, int act, int training, const void* dplane_mean, hipStream_t st);
@@ -246,12 +257,15 @@ hipError_t launch_bn_bwd(const void* x, const void* dout, const float* gamma, co
 // ---- dwconv.hip (depthwise convolution, NCHW) -----------------------------------------------------
 bool dwconv_supported(int K, int S);
 size_t dwconv_workspace_floats(int C, int K);
+// scale_shift (nullable, [C][2] fp32): the x the kernels see is act(x * scale[c] + shift[c]) rounded to the storage type, applied
+// while the tile is filled (forward and backward-weight only; the padding stays zero)
 hipError_t launch_dw_fwd(const void* x, const float* w, void* y, int N, int C, int H, int W, int OH, int OW, int K, int S,
-                         int pt, int pl, int dtype, hipStream_t st);
+                         int pt, int pl, int dtype, const float* scale_shift, int act, hipStream_t st);
 hipError_t launch_dw_bwd_data(const void* dy, const float* w, void* dx, int N, int C, int H, int W, int OH, int OW, int K,
                               int S, int pt, int pl, int dtype, hipStream_t st);
 hipError_t launch_dw_bwd_weight(const void* x, const void* dy, float* dw, float* ws, size_t ws_floats, int N, int C, int H,
-                                int W, int OH, int OW, int K, int S, int pt, int pl, int dtype, hipStream_t st);
+                                int W, int OH, int OW, int K, int S, int pt, int pl, int dtype, const float* scale_shift, int act,
+                                hipStream_t st);
 
 // ---- se.hip (squeeze-excite: per-plane mean, sigmoid gate) ----------------------------------------------
 hipError_t launch_plane_mean(const void* x, void* out, int NC, int HW, int dtype, hipStream_t st);

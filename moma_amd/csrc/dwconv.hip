@@ -89,11 +89,21 @@ __device__ __forceinline__ int fast_div(int i, int d, float inv_d) {
     return q;
 }
 
+// v as a value of storage type T holds it (what a store + reload of T would give back)
+template <typename T> __device__ __forceinline__ float storage_round(float v);
+template <> __device__ __forceinline__ float storage_round<float>(float v) { return v; }
+template <> __device__ __forceinline__ float storage_round<bf16_raw>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+
 // Fill tile rows r in [0, rows) of `np` planes: tile[(p*rows + r)*pitch + xo + col] = src_p[(y0 + r)*W + col] for image
 // rows, 0 for rows outside [0, H).  src_p = src + p*plane_stride.  Vector loads over each plane's contiguous row range.
-template <typename T, int VEC>
+// PRE (the source is a BatchNorm's input, the tile gets what the materialised act(BN(src)) would have held): every loaded element
+// becomes act(x * scale + shift), rounded to the storage type T, before it is stored; scale / shift of plane p = ssl[p * ss_stride],
+// ssl[p * ss_stride + 1] (in LDS).  Only loaded elements pass through it: halo columns and rows outside the image stay literal zeros,
+// the padding of the activation (act(shift) != 0 in general).
+template <typename T, int VEC, bool PRE = false>
 __device__ __forceinline__ void fill_tile(float* tile, const T* __restrict__ src, size_t plane_stride, int np, int H, int W,
-                                          int y0, int rows, int pitch, int xo, int lane, bool zero_rows) {
+                                          int y0, int rows, int pitch, int xo, int lane, bool zero_rows,
+                                          const float* ssl = nullptr, int ss_stride = 0, int act = 0) {
     const int ya = max(y0, 0), yb = min(y0 + rows, H);           // image rows present in the tile
     const int wv = W / VEC, nvpp = max(yb - ya, 0) * wv, total = nvpp * np;
     const float inv_nvpp = 1.0f / (float)max(nvpp, 1), inv_wv = 1.0f / (float)wv;
@@ -101,16 +111,24 @@ __device__ __forceinline__ void fill_tile(float* tile, const T* __restrict__ src
     for (int v0 = 0; v0 < total; v0 += 64 * U) {
         float val[U][VEC];
         int dst[U];
+        [[maybe_unused]] float sc[U], sf[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int v = min(v0 + u * 64 + lane, total - 1);
             const int p = fast_div(v, nvpp, inv_nvpp), e = v - p * nvpp, r = fast_div(e, wv, inv_wv), cv = e - r * wv;
             Vec<T, VEC>::ld(src + (size_t)p * plane_stride + (size_t)(ya + r) * W + cv * VEC, val[u]);
             dst[u] = (p * rows + (ya - y0) + r) * pitch + xo + cv * VEC;
+            if constexpr (PRE) { sc[u] = ssl[p * ss_stride]; sf[u] = ssl[p * ss_stride + 1]; }
         }
         // pin the loads as unconditional (else hipcc sinks each under the store's guard: load, wait, store, one by one)
 #pragma unroll
         for (int u = 0; u < U; ++u) asm volatile("" : "+v"(val[u][0]));
+        if constexpr (PRE) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) val[u][j] = storage_round<T>(act_fwd(fmaf(val[u][j], sc[u], sf[u]), act));
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (v0 + u * 64 + lane < total) lds_store<VEC>(tile + dst[u], val[u]);
@@ -126,14 +144,30 @@ __device__ __forceinline__ void fill_tile(float* tile, const T* __restrict__ src
     }
 }
 
-template <typename T, int K, int S, int R, bool FLIP, int VEC>
+// ssl[2p], ssl[2p+1] = scale, shift of plane plane0 + p's channel, p < np <= 8 (forward kernels: an item's planes can belong
+// to different channels)
+__device__ __forceinline__ void stage_scale_shift(float* ssl, const float* __restrict__ ss, int plane0, int np, int C, int lane) {
+    if (lane < np) {
+        const int c = (plane0 + lane) % C;
+        ssl[2 * lane] = ss[2 * c];
+        ssl[2 * lane + 1] = ss[2 * c + 1];
+    }
+}
+
+// PRE: x is the input of a BatchNorm + activation whose result is convolved (see fill_tile); ss = its scale_shift [C][2], the
+// item's planes' pairs are staged in LDS behind the taps
+template <typename T, int K, int S, int R, bool FLIP, int VEC, bool PRE>
 __global__ __launch_bounds__(DW_WAVES * 64) void dw_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
-                                                             T* __restrict__ y, DwShape sh) {
+                                                             T* __restrict__ y, DwShape sh, const float* __restrict__ ss,
+                                                             int act) {
+    static_assert(!(PRE && FLIP), "the prologue belongs to the forward convolution");
     extern __shared__ float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tfl = sh.PB * sh.IR * sh.pitch;                    // (multiple of 4 floats: tiles stay 16-B aligned)
-    float* tile = smem + wave * (tfl + ((sh.PB * K * K + 3) & ~3));
+    const int wfl = (sh.PB * K * K + 3) & ~3;
+    float* tile = smem + wave * (tfl + wfl + (PRE ? (2 * sh.PB + 3) & ~3 : 0));
     float* wl = tile + tfl;
+    [[maybe_unused]] float* ssl = wl + wfl;
     for (int i = lane; i < tfl; i += 64) tile[i] = 0.f;          // halo columns stay zero for good
     const int nitems = sh.ngroups * sh.nbands;
     const int nstrips = (sh.TH + R - 1) / R;
@@ -147,8 +181,9 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_fwd_kernel(const T* __restri
             const int p = i / (K * K), t = i - p * (K * K);
             wl[i] = w[((plane0 + p) % sh.C) * K * K + (FLIP ? K * K - 1 - t : t)];
         }
-        fill_tile<T, VEC>(tile, x + (size_t)plane0 * sh.H * sh.W, (size_t)sh.H * sh.W, np, sh.H, sh.W, oy0 * S - sh.pt, sh.IR,
-                          sh.pitch, XO, lane, sh.nbands > 1);
+        if constexpr (PRE) stage_scale_shift(ssl, ss, plane0, np, sh.C, lane);
+        fill_tile<T, VEC, PRE>(tile, x + (size_t)plane0 * sh.H * sh.W, (size_t)sh.H * sh.W, np, sh.H, sh.W, oy0 * S - sh.pt, sh.IR,
+                               sh.pitch, XO, lane, sh.nbands > 1, ssl, 2, act);
         __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): this wave's tile stores are done (no other wave reads it)
         const int nwork = nstrips * sh.OW;
         const float inv_ow = 1.0f / (float)sh.OW;
@@ -195,15 +230,19 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_fwd_kernel(const T* __restri
 // (plane, output row): it reads its K input rows ((OWT-1)*S + K values each) from the tile once, keeps them in
 // registers together with the K*K taps of its plane, and produces the OWT outputs of the row fully unrolled:
 // (K*((OWT-1)*S+K) + K*K) LDS reads and OWT*K*K FMAs per OWT outputs (K=5, OWT=14: 8.2 reads per output instead of 15).
-template <typename T, int K, int S, int OWT, bool FLIP, int VEC>
+template <typename T, int K, int S, int OWT, bool FLIP, int VEC, bool PRE>
 __global__ __launch_bounds__(DW_WAVES * 64) void dw_small_kernel(const T* __restrict__ x, const float* __restrict__ w,
-                                                               T* __restrict__ y, DwShape sh) {
+                                                               T* __restrict__ y, DwShape sh, const float* __restrict__ ss,
+                                                               int act) {
+    static_assert(!(PRE && FLIP), "the prologue belongs to the forward convolution");
     extern __shared__ float smem[];
     constexpr int IW = (OWT - 1) * S + K;        // input columns one output row needs
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tfl = sh.PB * sh.IR * sh.pitch;
-    float* tile = smem + wave * (tfl + ((sh.PB * K * K + 3) & ~3));
+    const int wfl = (sh.PB * K * K + 3) & ~3;
+    float* tile = smem + wave * (tfl + wfl + (PRE ? (2 * sh.PB + 3) & ~3 : 0));
     float* wl = tile + tfl;
+    [[maybe_unused]] float* ssl = wl + wfl;
     for (int i = lane; i < tfl; i += 64) tile[i] = 0.f;          // padding rows / columns stay zero for good
     const int p = lane / OWT, oy = lane - p * OWT;               // this lane's plane (of the item) and output row
     const int cbase = XO - sh.pl;
@@ -213,8 +252,9 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_small_kernel(const T* __rest
             const int pp = i / (K * K), t = i - pp * (K * K);
             wl[i] = w[((plane0 + pp) % sh.C) * K * K + (FLIP ? K * K - 1 - t : t)];
         }
-        fill_tile<T, VEC>(tile, x + (size_t)plane0 * sh.H * sh.W, (size_t)sh.H * sh.W, np, sh.H, sh.W, -sh.pt, sh.IR, sh.pitch,
-                          XO, lane, false);
+        if constexpr (PRE) stage_scale_shift(ssl, ss, plane0, np, sh.C, lane);
+        fill_tile<T, VEC, PRE>(tile, x + (size_t)plane0 * sh.H * sh.W, (size_t)sh.H * sh.W, np, sh.H, sh.W, -sh.pt, sh.IR, sh.pitch,
+                               XO, lane, false, ssl, 2, act);
         __builtin_amdgcn_s_waitcnt(0xc07f);
         if (p < np) {
             float wk[K * K];
@@ -308,16 +348,23 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_bwd_data_s2_kernel(const T* 
 // by one lane only).  Without the dy tile the x tile can be twice as tall at the same occupancy, which wins where the
 // halo is large (K = 5) or the planes are small; on the K = 3 layers with 56^2 / 112^2 planes the loads' latency in the
 // inner loop costs more than the shorter bands (measured both ways, scripts/bench_dw.py).
-template <typename T, int K, int S, int R, int VEC, int GVEC, bool GDIRECT>
+// PRE: x is the input of the BatchNorm + activation whose result was convolved (see fill_tile); every plane a workgroup visits
+// is channel c, whose scale / shift pair sits in LDS behind the tiles.  The dy tile and the GDIRECT loads are dy as it is.
+template <typename T, int K, int S, int R, int VEC, int GVEC, bool GDIRECT, bool PRE>
 __global__ __launch_bounds__(DW_WAVES * 64) void dw_bwd_weight_kernel(const T* __restrict__ x, const T* __restrict__ dy,
-                                                                    float* __restrict__ partial, DwShape sh, int N) {
+                                                                    float* __restrict__ partial, DwShape sh, int N,
+                                                                    const float* __restrict__ ss, int act) {
     extern __shared__ float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int xt = sh.PB * sh.IR * sh.pitch, gtn = GDIRECT ? 0 : sh.PB * sh.GR * sh.gpitch;
-    float* tile = smem + wave * (xt + gtn);
+    float* tile = smem + wave * (xt + gtn + (PRE ? 4 : 0));
     float* gt = tile + xt;
+    [[maybe_unused]] float* ssl = tile + xt + gtn;
     for (int i = lane; i < xt + gtn; i += 64) tile[i] = 0.f;
     const int c = blockIdx.y;
+    if constexpr (PRE) {
+        if (lane < 2) ssl[lane] = ss[2 * c + lane];
+    }
     const int nsplit = gridDim.x * DW_WAVES, split = blockIdx.x * DW_WAVES + wave;
     const int nstrips = (sh.TH + R - 1) / R;
     constexpr int CR = (R - 1) * S + K;
@@ -331,8 +378,8 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_bwd_weight_kernel(const T* _
         const int grp = item / sh.nbands, band = item - grp * sh.nbands;
         const int n0 = grp * sh.PB, np = min(sh.PB, N - n0);
         const int oy0 = band * sh.TH;
-        fill_tile<T, VEC>(tile, x + ((size_t)n0 * sh.C + c) * sh.H * sh.W, xs, np, sh.H, sh.W, oy0 * S - sh.pt, sh.IR, sh.pitch, XO,
-                          lane, sh.nbands > 1);
+        fill_tile<T, VEC, PRE>(tile, x + ((size_t)n0 * sh.C + c) * sh.H * sh.W, xs, np, sh.H, sh.W, oy0 * S - sh.pt, sh.IR, sh.pitch,
+                               XO, lane, sh.nbands > 1, ssl, 0, act);
         // dy rows of the band; rows past the plane's end are zero, so that a short last band contributes nothing
         if constexpr (!GDIRECT)
             fill_tile<T, GVEC>(gt, dy + ((size_t)n0 * sh.C + c) * sh.OH * sh.OW, gs, np, sh.OH, sh.OW, oy0, sh.GR, sh.gpitch, 0,
@@ -441,8 +488,9 @@ unsigned grid_for(long nitems) {
 // y (OH x OW) from x (H x W); also backward-data stride 1 with flip = true (then x = dy and y = dx)
 template <typename T, int K, int S>
 hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, int OH, int OW, int pt, int pl, bool flip,
-                 hipStream_t st) {
+                 const float* ss, int act, hipStream_t st) {
     constexpr int MAXV = 16 / sizeof(T);
+    if (flip && ss) return hipErrorInvalidValue;
     DwShape sh{};
     sh.NC = NC; sh.C = C; sh.H = H; sh.W = W; sh.OH = OH; sh.OW = OW; sh.pt = pt; sh.pl = pl;
     sh.pitch = round4(XO + max(W, (OW - 1) * S + K - pl) + 1);
@@ -453,14 +501,19 @@ hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, 
         sh.PB = OW == 7 ? 8 : 4;
         sh.pitch |= 1;           // lanes read rows one pitch apart: an odd pitch spreads them over all LDS banks
         sh.ngroups = (NC + sh.PB - 1) / sh.PB;
-        const size_t lds = (size_t)DW_WAVES * (sh.PB * sh.IR * sh.pitch + round4(sh.PB * K * K)) * sizeof(float);
-        if (lds <= (size_t)LDS_BUDGET) {
+        // the kernel is chosen on the size WITHOUT the prologue's scale / shift pairs: the call with them takes the kernel (and the
+        // summation order) of the call without, or fails
+        const size_t lds0 = (size_t)DW_WAVES * (sh.PB * sh.IR * sh.pitch + round4(sh.PB * K * K)) * sizeof(float);
+        const size_t lds = lds0 + (ss ? (size_t)DW_WAVES * round4(2 * sh.PB) * sizeof(float) : 0);
+        if (lds0 <= (size_t)LDS_BUDGET) {
+            if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
             const dim3 grid(grid_for(sh.ngroups)), block(DW_WAVES * 64);
             const int vec = 1;       // (odd pitch: element stores into the tile)
-#define MOMA_DW_SMALL(OWT, FL) hipLaunchKernelGGL((dw_small_kernel<T, K, S, OWT, FL, V>), grid, block, lds, st, x, w, y, sh)
+#define MOMA_DW_SMALL(OWT, FL, PR) \
+    hipLaunchKernelGGL((dw_small_kernel<T, K, S, OWT, FL, V, PR>), grid, block, lds, st, x, w, y, sh, ss, act)
             MOMA_DW_VEC_SWITCH(vec, MAXV, {
-                if (OW == 7) { if (flip) MOMA_DW_SMALL(7, true); else MOMA_DW_SMALL(7, false); }
-                else { if (flip) MOMA_DW_SMALL(14, true); else MOMA_DW_SMALL(14, false); }
+                if (OW == 7) { if (flip) MOMA_DW_SMALL(7, true, false); else if (ss) MOMA_DW_SMALL(7, false, true); else MOMA_DW_SMALL(7, false, false); }
+                else { if (flip) MOMA_DW_SMALL(14, true, false); else if (ss) MOMA_DW_SMALL(14, false, true); else MOMA_DW_SMALL(14, false, false); }
             })
 #undef MOMA_DW_SMALL
             return hipGetLastError();
@@ -472,14 +525,17 @@ hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, 
     sh.IR = (sh.TH - 1) * S + K;
     sh.PB = fit_planes(planes_per_item(OH, OW, sh.nbands), (long)sh.IR * sh.pitch);
     sh.ngroups = (NC + sh.PB - 1) / sh.PB;
-    const size_t lds = (size_t)DW_WAVES * (sh.PB * sh.IR * sh.pitch + round4(sh.PB * K * K)) * sizeof(float);
+    const size_t lds = (size_t)DW_WAVES * (sh.PB * sh.IR * sh.pitch + round4(sh.PB * K * K) + (ss ? round4(2 * sh.PB) : 0)) *
+                       sizeof(float);
     if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
     const dim3 grid(grid_for((long)sh.ngroups * sh.nbands)), block(DW_WAVES * 64);
     const int vec = pick_vec(W, sizeof(T), x);
-#define MOMA_DW_GO(RR, FL) hipLaunchKernelGGL((dw_fwd_kernel<T, K, S, RR, FL, V>), grid, block, lds, st, x, w, y, sh)
+#define MOMA_DW_GO(RR, FL, PR) \
+    hipLaunchKernelGGL((dw_fwd_kernel<T, K, S, RR, FL, V, PR>), grid, block, lds, st, x, w, y, sh, ss, act)
     MOMA_DW_VEC_SWITCH(vec, MAXV, {
-        if (flip) { if (R == 4) MOMA_DW_GO(4, true); else if (R == 2) MOMA_DW_GO(2, true); else MOMA_DW_GO(1, true); }
-        else { if (R == 4) MOMA_DW_GO(4, false); else if (R == 2) MOMA_DW_GO(2, false); else MOMA_DW_GO(1, false); }
+        if (flip) { if (R == 4) MOMA_DW_GO(4, true, false); else if (R == 2) MOMA_DW_GO(2, true, false); else MOMA_DW_GO(1, true, false); }
+        else if (ss) { if (R == 4) MOMA_DW_GO(4, false, true); else if (R == 2) MOMA_DW_GO(2, false, true); else MOMA_DW_GO(1, false, true); }
+        else { if (R == 4) MOMA_DW_GO(4, false, false); else if (R == 2) MOMA_DW_GO(2, false, false); else MOMA_DW_GO(1, false, false); }
     })
 #undef MOMA_DW_GO
     return hipGetLastError();
@@ -513,7 +569,7 @@ hipError_t bwd_data_s2_t(const T* dy, const float* w, T* dx, int NC, int C, int 
 
 template <typename T, int K, int S>
 hipError_t bwd_weight_t(const T* x, const T* dy, float* dw, float* ws, size_t ws_floats, int N, int C, int H, int W, int OH,
-                        int OW, int pt, int pl, hipStream_t st) {
+                        int OW, int pt, int pl, const float* ss, int act, hipStream_t st) {
     constexpr int MAXV = 16 / sizeof(T);
     DwShape sh{};
     sh.NC = N * C; sh.C = C; sh.H = H; sh.W = W; sh.OH = OH; sh.OW = OW; sh.pt = pt; sh.pl = pl;
@@ -527,7 +583,7 @@ hipError_t bwd_weight_t(const T* x, const T* dy, float* dw, float* ws, size_t ws
     sh.GR = gdirect ? 0 : sh.TH;
     sh.PB = fit_planes(min(planes_per_item(OH, OW, sh.nbands), N), (long)sh.IR * sh.pitch + (long)sh.GR * sh.gpitch);
     sh.ngroups = (N + sh.PB - 1) / sh.PB;          // groups of images (per channel)
-    const size_t lds = (size_t)DW_WAVES * sh.PB * (sh.IR * sh.pitch + sh.GR * sh.gpitch) * sizeof(float);
+    const size_t lds = (size_t)DW_WAVES * (sh.PB * (sh.IR * sh.pitch + sh.GR * sh.gpitch) + (ss ? 4 : 0)) * sizeof(float);
     if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
     // ~8192 waves in all, at least one item per wave, partials must fit the workspace
     long nsplit_wg = max(1L, min((long)(2048 + C - 1) / C, ((long)sh.ngroups * sh.nbands + DW_WAVES - 1) / DW_WAVES));
@@ -536,12 +592,15 @@ hipError_t bwd_weight_t(const T* x, const T* dy, float* dw, float* ws, size_t ws
     const dim3 grid((unsigned)nsplit_wg, C), block(DW_WAVES * 64);
     const int vec = pick_vec(W, sizeof(T), x), gvec = pick_vec(OW, sizeof(T), dy);
     // (the dy tile takes the x tile's vector width when that divides OW too, else scalar: keeps the instantiations down)
-#define MOMA_DW_GO(RR, GV, GD) hipLaunchKernelGGL((dw_bwd_weight_kernel<T, K, S, RR, V, GV, GD>), grid, block, lds, st, x, dy, ws, sh, N)
+#define MOMA_DW_GO1(RR, GV, GD, PR) \
+    hipLaunchKernelGGL((dw_bwd_weight_kernel<T, K, S, RR, V, GV, GD, PR>), grid, block, lds, st, x, dy, ws, sh, N, ss, act)
+#define MOMA_DW_GO(RR, GV, GD) { if (ss) MOMA_DW_GO1(RR, GV, GD, true); else MOMA_DW_GO1(RR, GV, GD, false); }
     MOMA_DW_VEC_SWITCH(vec, MAXV, {
-        if (gdirect) { if (R == 4) MOMA_DW_GO(4, 1, true); else if (R == 2) MOMA_DW_GO(2, 1, true); else MOMA_DW_GO(1, 1, true); }
-        else if (gvec >= V) { if (R == 4) MOMA_DW_GO(4, V, false); else if (R == 2) MOMA_DW_GO(2, V, false); else MOMA_DW_GO(1, V, false); }
-        else { if (R == 4) MOMA_DW_GO(4, 1, false); else if (R == 2) MOMA_DW_GO(2, 1, false); else MOMA_DW_GO(1, 1, false); }
+        if (gdirect) { if (R == 4) MOMA_DW_GO(4, 1, true) else if (R == 2) MOMA_DW_GO(2, 1, true) else MOMA_DW_GO(1, 1, true) }
+        else if (gvec >= V) { if (R == 4) MOMA_DW_GO(4, V, false) else if (R == 2) MOMA_DW_GO(2, V, false) else MOMA_DW_GO(1, V, false) }
+        else { if (R == 4) MOMA_DW_GO(4, 1, false) else if (R == 2) MOMA_DW_GO(2, 1, false) else MOMA_DW_GO(1, 1, false) }
     })
+#undef MOMA_DW_GO1
 #undef MOMA_DW_GO
     const int total = C * K * K;
     hipLaunchKernelGGL(dw_bwd_weight_finalize_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ws, dw, total,
@@ -561,13 +620,13 @@ size_t dwconv_workspace_floats(int C, int K) { return (size_t)C * 64 * DW_WAVES 
     return hipErrorInvalidValue;
 
 hipError_t launch_dw_fwd(const void* x, const float* w, void* y, int N, int C, int H, int W, int OH, int OW, int K, int S,
-                         int pt, int pl, int dtype, hipStream_t st) {
+                         int pt, int pl, int dtype, const float* scale_shift, int act, hipStream_t st) {
     if (dtype == MOMA_DT_BF16) {
-#define CALL(KK, SS) fwd_t<bf16_raw, KK, SS>((const bf16_raw*)x, w, (bf16_raw*)y, N * C, C, H, W, OH, OW, pt, pl, false, st)
+#define CALL(KK, SS) fwd_t<bf16_raw, KK, SS>((const bf16_raw*)x, w, (bf16_raw*)y, N * C, C, H, W, OH, OW, pt, pl, false, scale_shift, act, st)
         MOMA_DW_DISPATCH(CALL)
 #undef CALL
     }
-#define CALL(KK, SS) fwd_t<float, KK, SS>((const float*)x, w, (float*)y, N * C, C, H, W, OH, OW, pt, pl, false, st)
+#define CALL(KK, SS) fwd_t<float, KK, SS>((const float*)x, w, (float*)y, N * C, C, H, W, OH, OW, pt, pl, false, scale_shift, act, st)
     MOMA_DW_DISPATCH(CALL)
 #undef CALL
 }
@@ -577,11 +636,11 @@ hipError_t launch_dw_bwd_data(const void* dy, const float* w, void* dx, int N, i
     if (S == 1) {
         // correlation of dy with the flipped filter, padding K-1-pt / K-1-pl; result plane = the input plane
         if (dtype == MOMA_DT_BF16) {
-            if (K == 3) return fwd_t<bf16_raw, 3, 1>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, OH, OW, H, W, 2 - pt, 2 - pl, true, st);
-            if (K == 5) return fwd_t<bf16_raw, 5, 1>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, OH, OW, H, W, 4 - pt, 4 - pl, true, st);
+            if (K == 3) return fwd_t<bf16_raw, 3, 1>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, OH, OW, H, W, 2 - pt, 2 - pl, true, nullptr, 0, st);
+            if (K == 5) return fwd_t<bf16_raw, 5, 1>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, OH, OW, H, W, 4 - pt, 4 - pl, true, nullptr, 0, st);
         } else {
-            if (K == 3) return fwd_t<float, 3, 1>((const float*)dy, w, (float*)dx, N * C, C, OH, OW, H, W, 2 - pt, 2 - pl, true, st);
-            if (K == 5) return fwd_t<float, 5, 1>((const float*)dy, w, (float*)dx, N * C, C, OH, OW, H, W, 4 - pt, 4 - pl, true, st);
+            if (K == 3) return fwd_t<float, 3, 1>((const float*)dy, w, (float*)dx, N * C, C, OH, OW, H, W, 2 - pt, 2 - pl, true, nullptr, 0, st);
+            if (K == 5) return fwd_t<float, 5, 1>((const float*)dy, w, (float*)dx, N * C, C, OH, OW, H, W, 4 - pt, 4 - pl, true, nullptr, 0, st);
         }
         return hipErrorInvalidValue;
     }
@@ -596,13 +655,14 @@ hipError_t launch_dw_bwd_data(const void* dy, const float* w, void* dx, int N, i
 }
 
 hipError_t launch_dw_bwd_weight(const void* x, const void* dy, float* dw, float* ws, size_t ws_floats, int N, int C, int H,
-                                int W, int OH, int OW, int K, int S, int pt, int pl, int dtype, hipStream_t st) {
+                                int W, int OH, int OW, int K, int S, int pt, int pl, int dtype, const float* scale_shift, int act,
+                                hipStream_t st) {
     if (dtype == MOMA_DT_BF16) {
-#define CALL(KK, SS) bwd_weight_t<bf16_raw, KK, SS>((const bf16_raw*)x, (const bf16_raw*)dy, dw, ws, ws_floats, N, C, H, W, OH, OW, pt, pl, st)
+#define CALL(KK, SS) bwd_weight_t<bf16_raw, KK, SS>((const bf16_raw*)x, (const bf16_raw*)dy, dw, ws, ws_floats, N, C, H, W, OH, OW, pt, pl, scale_shift, act, st)
         MOMA_DW_DISPATCH(CALL)
 #undef CALL
     }
-#define CALL(KK, SS) bwd_weight_t<float, KK, SS>((const float*)x, (const float*)dy, dw, ws, ws_floats, N, C, H, W, OH, OW, pt, pl, st)
+#define CALL(KK, SS) bwd_weight_t<float, KK, SS>((const float*)x, (const float*)dy, dw, ws, ws_floats, N, C, H, W, OH, OW, pt, pl, scale_shift, act, st)
     MOMA_DW_DISPATCH(CALL)
 #undef CALL
 }

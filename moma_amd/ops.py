@@ -780,6 +780,83 @@ def dwconv(x, weight, stride: int, pad_top: int, pad_left: int, out_h: int, out_
 
 
 # ------------------------------------------------------------------------------------------------
+# BatchNorm2d + activation applied INSIDE the depthwise convolution that consumes it (the _bn0 -> _depthwise_conv
+# pair of an MBConv block): the activation tensor between the two is never written
+# ------------------------------------------------------------------------------------------------
+class _BNActDWConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, act, w, stride, pad_top,
+                pad_left, out_h, out_w):
+        lib = _lib.load()
+        _dev(x, "x", dtype=None, contiguous=False)
+        _dev(w, "weight")
+        if x.dim() != 4 or x.dtype not in _DT_CODES or w.dim() != 4 or w.shape[1] != 1 or w.shape[0] != x.shape[1] \
+                or w.shape[2] != w.shape[3]:
+            raise ValueError(f"bn_act_dwconv: x {tuple(x.shape)} {x.dtype}, weight {tuple(w.shape)}")
+        x = x.contiguous()
+        w = w.contiguous()
+        N, Cc, H, W = x.shape
+        K = w.shape[2]
+        dev = x.device
+        save_mean = torch.empty(Cc, device=dev, dtype=torch.float32)
+        save_invstd = torch.empty(Cc, device=dev, dtype=torch.float32)
+        scale_shift = torch.empty(Cc, 2, device=dev, dtype=torch.float32)
+        ws = torch.empty(lib.moma_bn_workspace_bytes(Cc), device=dev, dtype=torch.uint8)
+        check(lib.moma_bn_prepare(_ptr(x), _ptr(weight), _ptr(bias), _ptr(running_mean), _ptr(running_var), _ptr(save_mean),
+                                  _ptr(save_invstd), _ptr(scale_shift), _ptr(ws), ws.numel(), N, Cc, H * W,
+                                  _DT_CODES[x.dtype], int(training), float(momentum), float(eps), _stream()), "moma_bn_prepare")
+        y = torch.empty(N, Cc, out_h, out_w, device=dev, dtype=x.dtype)
+        check(lib.moma_dwconv_fwd_pre(_ptr(x), _ptr(w), _ptr(y), N, Cc, H, W, out_h, out_w, K, stride, pad_top, pad_left,
+                                      _DT_CODES[x.dtype], _ptr(scale_shift), act, _stream()), "moma_dwconv_fwd_pre")
+        ctx.save_for_backward(x, weight, bias, save_mean, save_invstd, scale_shift, w)
+        ctx.cfg = (N, Cc, H, W, out_h, out_w, K, stride, pad_top, pad_left, act, int(training))
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, weight, bias, save_mean, save_invstd, scale_shift, w = ctx.saved_tensors
+        N, Cc, H, W, OH, OW, K, stride, pt, pl, act, training = ctx.cfg
+        dx = dgamma = dbeta = dw = None
+        if dy is None:
+            return (None,) * 15
+        dy = dy.contiguous()
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        dev, dt = x.device, _DT_CODES[x.dtype]
+        want_gamma = weight is not None and ctx.needs_input_grad[1]
+        want_beta = bias is not None and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[0] or want_gamma or want_beta:
+            da = torch.empty_like(x)            # gradient w.r.t. the activation that was never stored
+            check(lib.moma_dwconv_bwd_data(_ptr(dy), _ptr(w), _ptr(da), N, Cc, H, W, OH, OW, K, stride, pt, pl, dt,
+                                           _stream()), "moma_dwconv_bwd_data")
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            dgamma = torch.empty(Cc, device=dev, dtype=torch.float32) if want_gamma else None
+            dbeta = torch.empty(Cc, device=dev, dtype=torch.float32) if want_beta else None
+            ws = torch.empty(lib.moma_bn_workspace_bytes(Cc), device=dev, dtype=torch.uint8)
+            check(lib.moma_bn_bwd(_ptr(x), _ptr(da), _ptr(weight), _ptr(bias), _ptr(save_mean), _ptr(save_invstd), _ptr(dx),
+                                  _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), N, Cc, H * W, dt, act, training, None,
+                                  _stream()), "moma_bn_bwd")
+        if ctx.needs_input_grad[9]:
+            dw = torch.empty_like(w)
+            ws = torch.empty(lib.moma_dwconv_workspace_bytes(Cc, K), device=dev, dtype=torch.uint8)
+            check(lib.moma_dwconv_bwd_weight_pre(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel(), N, Cc, H, W, OH, OW, K,
+                                                 stride, pt, pl, dt, _ptr(scale_shift), act, _stream()),
+                  "moma_dwconv_bwd_weight_pre")
+        return dx, dgamma, dbeta, None, None, None, None, None, None, dw, None, None, None, None, None
+
+
+def bn_act_dwconv(x, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float, act, w_dw,
+                  stride: int, pad_top: int, pad_left: int, out_h: int, out_w: int):
+    """dwconv(bn_act(x, ...), w_dw, ...) bit for bit, in one pass less over x and without the tensor in between: the
+    depthwise kernels normalise and activate every element as they read it.  Running statistics are updated in place
+    when training; the backward keeps x and the statistics only."""
+    return _BNActDWConv.apply(x, weight, bias, running_mean, running_var, bool(training), momentum, eps, ACT_CODES[act],
+                              w_dw, int(stride), int(pad_top), int(pad_left), int(out_h), int(out_w))
+
+
+# ------------------------------------------------------------------------------------------------
 # Squeeze-excite helpers (include/moma_hip.h "SE")
 # ------------------------------------------------------------------------------------------------
 class _PlaneMean(torch.autograd.Function):
