@@ -269,6 +269,39 @@ int moma_at_bwd(const void* f, const float* g_a, const float* g_loss, void* dF, 
                 int dtype, int layout, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * NST  Neuron Selectivity Transfer (`--distill nst`) on one pair of feature maps on a COMMON grid -- replaces NSTLoss.nst_loss
+ *      behind its pooling (distiller_zoo/NST.py: view -> F.normalize(dim=2) -> poly_kernel(f_s, f_s).mean()
+ *      - 2 poly_kernel(f_s, f_t).mean(), the reference's full_loss = False branch) and its autograd backward to f_s.
+ *      For f_s [B,Cs,H,W], f_t [B,Ct,H,W], P = H W, per image X = f_s[b] as [Cs,P], Y = f_t[b] as [Ct,P]:
+ *          n_i = max(|X_i|_2, 1e-12)    m_j = max(|Y_j|_2, 1e-12)
+ *          G[b,i,j] = X_i . X_j / (n_i n_j) for j < Cs (Gss),  X_i . Y_(j-Cs) / (n_i m_(j-Cs)) for j >= Cs (Gst)
+ *          t1 = mean_(b,i,j) Gss^2    t2 = mean_(b,i,j) Gst^2    loss = t1 - 2 t2
+ *          dX_i = g_loss (1/n_i) [ sum_j (a Gss_ij / n_j) X_j - sum_j (c Gst_ij / m_j) Y_j - (r_i / n_i) X_i ]
+ *          a = 4 / (B Cs^2)   c = 4 / (B Cs Ct)   r_i = a sum_j Gss_ij^2 - c sum_j Gst_ij^2     (a row with |X_i| = 0: dX_i = 0)
+ *      f_s, f_t, dF_s: MOMA_DT_F32 or MOMA_DT_BF16 and MOMA_LAYOUT_NCHW or MOMA_LAYOUT_NHWC, each chosen per side (dF_s as
+ *      f_s), dense, aligned to their element size -- 16-byte accesses where the address and the contiguous extent (P, or C) allow,
+ *      element accesses otherwise.  Everything else is fp32.  All products in fp32 on the f32-input MFMA whatever the storage; the
+ *      normalisation is applied to the raw Gram in its epilogue (no normalised copy of a map exists).  Cs, Ct <= MOMA_NST_MAX_C
+ *      (wider maps: MOMA_E_UNSUPPORTED).  No atomics: results are bitwise reproducible.
+ *
+ * workspace     G [B, Cs, Cs + Ct] fp32 = moma_nst_workspace_bytes() = B Cs (Cs + Ct) 4 bytes, 4-byte aligned; moma_nst_gram
+ *               writes it, moma_nst_bwd reads it.
+ * moma_nst_gram both maps, requested once per block of MOMA_NST_ROW_BLOCK student rows (ceil(Cs / 32) times) -> G, norms
+ *               [B, Cs + Ct] (n then m, clamped), rows [B, Cs, 2] (sum_j Gss_ij^2, sum_j Gst_ij^2), partials
+ *               [B, ceil(Cs / MOMA_NST_ROW_BLOCK), 2] (a workgroup's sums of both), terms [2] = (t1, t2), loss [1].
+ * moma_nst_bwd  dF_s from one read of both maps, G, norms and rows; g_loss is a DEVICE scalar (the upstream gradient of the loss,
+ *               e.g. a GradScaler factor): nothing is read back to the host.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_NST_MAX_C = 256, MOMA_NST_ROW_BLOCK = 32 };
+size_t moma_nst_workspace_bytes(int B, int Cs, int Ct);
+int moma_nst_gram(const void* f_s, const void* f_t, int B, int Cs, int Ct, int P, int dtype_s, int layout_s, int dtype_t,
+                  int layout_t, void* workspace, size_t workspace_bytes, float* norms, float* rows, float* partials, float* terms,
+                  float* loss, moma_stream_t stream);
+int moma_nst_bwd(const void* f_s, const void* f_t, const void* workspace, size_t workspace_bytes, const float* norms,
+                 const float* rows, const float* g_loss, void* dF_s, int B, int Cs, int Ct, int P, int dtype_s, int layout_s,
+                 int dtype_t, int layout_t, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1  batch-token multi-head attention -- replaces Attention.forward
  *     (MoMA/criterion_moco_att.py:153-167) and its autograd backward.
  *     x [N,d] -> qkv = x Wqkv^T + bqkv -> per head softmax(q k^T * hd^-1/2) v -> y = a Wproj^T + bproj.

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("MOMA_HIP_LIB", os.path.join(_HERE, "lib", "libmoma_hi
 PREC_F32, PREC_BF16 = 0, 1
 DT_F32, DT_BF16 = 0, 1
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+NST_MAX_C, NST_ROW_BLOCK = 256, 32
 MHA_SAVE_PROBS, MHA_SAVE_LSE = 0, 1
 ABI_VERSION = 4
 EMA_BLOCK_ELEMS = 4096
@@ -55,6 +56,9 @@ SIGNATURES = {
     "moma_at_map": (_i, [_p, _p] + [_i] * 8 + [_p, _z, _p]),
     "moma_at_pair": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "moma_at_bwd": (_i, [_p, _p, _p, _p] + [_i] * 8 + [_p]),
+    "moma_nst_workspace_bytes": (_z, [_i] * 3),
+    "moma_nst_gram": (_i, [_p, _p] + [_i] * 8 + [_p, _z, _p, _p, _p, _p, _p, _p]),
+    "moma_nst_bwd": (_i, [_p, _p, _p, _z, _p, _p, _p, _p] + [_i] * 8 + [_p]),
     "moma_mha_fwd": (_i,[_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "moma_mha_saved_state": (_i, [_i, _i, _i, _i]),
     "moma_mha_pack_bytes": (_z, [_i]),

@@ -723,4 +723,50 @@ int moma_at_bwd(const void* f, const float* g_a, const float* g_loss, void* dF, 
     return hip_rc(launch_at_bwd(f, g_a, g_loss, dF, B, C, H, W, oh, ow, dtype, layout, (hipStream_t)stream));
 }
 
+// ---- Neuron Selectivity Transfer -----------------------------------------------------------------------------------------------
+static int nst_check(int B, int Cs, int Ct, int P, int dtype_s, int layout_s, int dtype_t, int layout_t) {
+    if (B <= 0 || Cs <= 0 || Ct <= 0 || P <= 0) return MOMA_E_SHAPE;
+    if (bad_dt(dtype_s) || bad_dt(dtype_t)) return MOMA_E_DTYPE;
+    if ((layout_s != MOMA_LAYOUT_NCHW && layout_s != MOMA_LAYOUT_NHWC) || (layout_t != MOMA_LAYOUT_NCHW && layout_t != MOMA_LAYOUT_NHWC))
+        return MOMA_E_UNSUPPORTED;
+    if (Cs > MOMA_NST_MAX_C || Ct > MOMA_NST_MAX_C) return MOMA_E_UNSUPPORTED;
+    if (P > INT32_MAX / 2) return MOMA_E_UNSUPPORTED;                          // (pixel indices of one image are ints)
+    if ((long long)B * nst_row_blocks(Cs) > INT32_MAX || (long long)B * nst_pixel_tiles(P) > INT32_MAX) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_nst_workspace_bytes(int B, int Cs, int Ct) {
+    if (B <= 0 || Cs <= 0 || Ct <= 0 || Cs > MOMA_NST_MAX_C || Ct > MOMA_NST_MAX_C) return 0;
+    return nst_workspace_bytes(B, Cs, Ct);
+}
+
+int moma_nst_gram(const void* f_s, const void* f_t, int B, int Cs, int Ct, int P, int dtype_s, int layout_s, int dtype_t,
+                  int layout_t, void* workspace, size_t workspace_bytes, float* norms, float* rows, float* partials, float* terms,
+                  float* loss, moma_stream_t stream) {
+    if (!f_s || !f_t || !workspace || !norms || !rows || !partials || !terms || !loss) return MOMA_E_NULL;
+    const int rc = nst_check(B, Cs, Ct, P, dtype_s, layout_s, dtype_t, layout_t);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < nst_workspace_bytes(B, Cs, Ct)) return MOMA_E_WORKSPACE;
+    if (misaligned(f_s, dtype_s == MOMA_DT_BF16 ? 2 : 4) || misaligned(f_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(workspace, 4) ||
+        misaligned(norms, 4) || misaligned(rows, 4) || misaligned(partials, 4) || misaligned(terms, 4) || misaligned(loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_nst_gram(f_s, f_t, B, Cs, Ct, P, dtype_s, layout_s, dtype_t, layout_t, (float*)workspace, norms, rows, partials,
+                                  terms, loss, (hipStream_t)stream));
+}
+
+int moma_nst_bwd(const void* f_s, const void* f_t, const void* workspace, size_t workspace_bytes, const float* norms,
+                 const float* rows, const float* g_loss, void* dF_s, int B, int Cs, int Ct, int P, int dtype_s, int layout_s,
+                 int dtype_t, int layout_t, moma_stream_t stream) {
+    if (!f_s || !f_t || !workspace || !norms || !rows || !g_loss || !dF_s) return MOMA_E_NULL;
+    const int rc = nst_check(B, Cs, Ct, P, dtype_s, layout_s, dtype_t, layout_t);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < nst_workspace_bytes(B, Cs, Ct)) return MOMA_E_WORKSPACE;
+    const size_t eb = dtype_s == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(f_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(workspace, 4) ||
+        misaligned(norms, 4) || misaligned(rows, 4) || misaligned(g_loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_nst_bwd(f_s, f_t, (const float*)workspace, norms, rows, g_loss, dF_s, B, Cs, Ct, P, dtype_s, layout_s, dtype_t,
+                                 layout_t, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -202,6 +202,15 @@ hipError_t launch_at_pair(const float* a_s, const float* a_t, int B, int n, floa
 hipError_t launch_at_bwd(const void* f, const float* g_a, const float* g_loss, void* dF, int B, int C, int H, int W, int oh, int ow,
                          int dtype, int layout, hipStream_t st);
 
+// ---- nst.hip (Neuron Selectivity Transfer: per-image normalised Gram of a feature pair, its loss, the student's gradient) ------
+size_t nst_workspace_bytes(int B, int Cs, int Ct);
+long long nst_row_blocks(int Cs);
+long long nst_pixel_tiles(int P);
+hipError_t launch_nst_gram(const void* fs, const void* ft, int B, int Cs, int Ct, int P, int dt_s, int lay_s, int dt_t, int lay_t,
+                           float* G, float* norms, float* rows, float* partials, float* terms, float* loss, hipStream_t st);
+hipError_t launch_nst_bwd(const void* fs, const void* ft, const float* G, const float* norms, const float* rows, const float* g_loss,
+                          void* dF, int B, int Cs, int Ct, int P, int dt_s, int lay_s, int dt_t, int lay_t, hipStream_t st);
+
 // ---- infonce_fused.hip (one-pass flash-style kernel) ----------------------------------------------
 bool infonce_flash_supported(int B, int d, int K, int qdtype, int prec);
 size_t infonce_flash_workspace_bytes(int B, int d, int K);

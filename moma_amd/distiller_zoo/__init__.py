@@ -1,4 +1,5 @@
 from .AT import Attention
 from .KD import DistillKL
+from .NST import NSTLoss
 
-__all__ = ["Attention", "DistillKL"]
+__all__ = ["Attention", "DistillKL", "NSTLoss"]

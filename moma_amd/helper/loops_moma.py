@@ -19,6 +19,11 @@ maps of the student's forward and the teacher's single no-grad forward, handed t
 backbones produced (bf16 under `--amp bf16`, channels_last under `--channels_last`: csrc/attention.hip reads both natively).  No
 auxiliary module, no EMA, no ContrastTrainer; the teacher's forward is eager (its HIP-graph replay hands out the last feature only)
 and so is the step.
+
+`--distill nst` (reference :150-154): the KD term is sum(NSTLoss(feat_s[1:-2], feat_t[1:-2])) -- Neuron Selectivity Transfer over the
+intermediate feature maps short of the last one, through the same teacher branch as `attention` (one eager no-grad forward with
+every feature map, dtype and memory format as the backbones left them: csrc/nst.hip reads fp32 / bf16 and NCHW / channels_last per
+side).  Nothing to train besides the student, no memory; the step is eager.
 """
 from __future__ import print_function
 
@@ -109,10 +114,11 @@ class MomaStep:
         """teacher forward #1 (:270-272), then the moma branch's no-grad part (:309-320, :327-329)."""
         opt, trainer, criterion_kd, model_t = self.opt, self.trainer, self.criterion_kd, self.model_t
         with self.autocast(), torch.no_grad():
-            if opt.distill == "attention":    # (:270-272, :287-292) every feature map, as autocast left it: an eager forward
+            if opt.distill in ("attention", "nst"):    # (:270-272, :287-292 / :150-154) every feature map, as autocast left it: an eager forward
                 ft, lt = teacher(images, is_feat=True, full_feats=True) if isinstance(teacher, GraphedInference) \
                     else teacher(images, is_feat=True)
-                return lt.float(), [f.detach() for f in ft[1:-1]], None          # g_t rides in the key slot
+                ft = ft[1:-1] if opt.distill == "attention" else ft[1:-2]
+                return lt.float(), [f.detach() for f in ft], None                # g_t rides in the key slot
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
             return lt.float(), ft[-1].float(), None
@@ -167,6 +173,8 @@ class MomaStep:
             f_s = feat_s[-1].float()                                                      # (:304)
         if opt.distill == "attention":
             out["g_s"] = list(feat_s[1:-1])                                               # (:289)
+        if opt.distill == "nst":
+            out["g_s"] = list(feat_s[1:-2])                                               # (:151)
         if opt.distill == "moma":
             with self.autocast():
                 f_s = criterion_kd.embed_s(feat_s[-1])                                    # (:323-324)
@@ -226,7 +234,7 @@ class MomaStep:
         if opt.distill == "crd":                                                          # (:303-306) f_t rides in fw["k"]
             with self.autocast():
                 return criterion_kd(fw["f_s"], fw["k"], fw["index"], fw["contrast_idx"]).float()
-        if opt.distill == "attention":                                                    # (:287-292) g_t rides in fw["k"]
+        if opt.distill in ("attention", "nst"):                                           # (:287-292 / :150-154) g_t rides in fw["k"]
             return sum(criterion_kd(fw["g_s"], fw["k"])).float()
         if opt.distill != "moma":
             raise NotImplementedError(opt.distill)

@@ -1069,11 +1069,11 @@ def crd_update_(memory_v1, memory_v2, v1, v2, y, momentum: float, bad=None) -> N
 # ------------------------------------------------------------------------------------------------
 # Attention Transfer: spatial attention maps of a feature pair   (distiller_zoo/AT.py, helper/loops_moma.py:287-292)
 # ------------------------------------------------------------------------------------------------
-def _at_side(f, name):
+def _at_side(f, name, op="attention_loss"):
     """-> (dense tensor, layout code): contiguous NCHW and channels_last are taken as they are, any other dense layout is copied"""
     _dev(f, name, dtype=None, contiguous=False)
     if f.dim() != 4 or f.dtype not in _DT_CODES:
-        raise TypeError(f"attention_loss: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+        raise TypeError(f"{op}: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
     if f.is_contiguous():
         return f, _lib.LAYOUT_NCHW
     if f.is_contiguous(memory_format=torch.channels_last):
@@ -1163,3 +1163,74 @@ def attention_loss(f_s, f_t) -> torch.Tensor:
         if small.shape[3] != ow:
             raise ValueError(f"attention_loss: the smaller map {tuple(small.shape)} is not square: no common {oh} x {ow} grid")
     return _AttentionLoss.apply(f_s, f_t, int(oh), int(ow))
+
+
+# ------------------------------------------------------------------------------------------------
+# Neuron Selectivity Transfer: per-image normalised Gram of a feature pair   (distiller_zoo/NST.py, helper/loops_moma.py:150-154)
+# ------------------------------------------------------------------------------------------------
+class _NSTLoss(torch.autograd.Function):
+    """nst_gram (G, norms, row sums, loss) in the forward; nst_bwd (dF_s from the raw maps and G) in the backward."""
+
+    @staticmethod
+    def forward(ctx, f_s, f_t):
+        lib = _lib.load()
+        f_s, lay_s = _at_side(f_s, "f_s", "nst_loss")
+        f_t, lay_t = _at_side(f_t, "f_t", "nst_loss")
+        B, Cs, H, W = f_s.shape
+        Ct = f_t.shape[1]
+        if f_t.shape[0] != B or tuple(f_t.shape[2:]) != (H, W):
+            raise ValueError(f"nst_loss: f_s {tuple(f_s.shape)} and f_t {tuple(f_t.shape)} are not on a common grid")
+        dev, P = f_s.device, H * W
+        codes = (_DT_CODES[f_s.dtype], lay_s, _DT_CODES[f_t.dtype], lay_t)
+        with _timed("moma_nst_fwd"):
+            n = lib.moma_nst_workspace_bytes(B, Cs, Ct)
+            if n == 0:
+                raise ValueError(f"nst_loss: the kernels take at most {_lib.NST_MAX_C} channels per side, got {Cs} and {Ct}")
+            G = torch.empty(n // 4, device=dev, dtype=torch.float32)
+            norms = torch.empty(B, Cs + Ct, device=dev, dtype=torch.float32)
+            rows = torch.empty(B, Cs, 2, device=dev, dtype=torch.float32)
+            partials = torch.empty(B, -(-Cs // _lib.NST_ROW_BLOCK), 2, device=dev, dtype=torch.float32)
+            terms = torch.empty(2, device=dev, dtype=torch.float32)
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            check(lib.moma_nst_gram(_ptr(f_s), _ptr(f_t), B, Cs, Ct, P, *codes, _ptr(G), n, _ptr(norms), _ptr(rows), _ptr(partials),
+                                    _ptr(terms), _ptr(loss), _stream()), "moma_nst_gram")
+        # (nst_loss, the only caller, refuses an f_t that wants a gradient: backward runs only where f_s does, with these saved)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(f_s, f_t, G, norms, rows)
+        ctx.codes = codes
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        f_s, f_t, G, norms, rows = ctx.saved_tensors
+        B, Cs, H, W = f_s.shape
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        with _timed("moma_nst_bwd"):
+            dF = torch.empty_like(f_s)                # (same dtype, same strides: NCHW or channels_last)
+            check(lib.moma_nst_bwd(_ptr(f_s), _ptr(f_t), _ptr(G), G.numel() * 4, _ptr(norms), _ptr(rows), _ptr(g), _ptr(dF), B, Cs,
+                                   f_t.shape[1], H * W, *ctx.codes, _stream()), "moma_nst_bwd")
+        return dF, None
+
+
+def nst_loss(f_s, f_t) -> torch.Tensor:
+    """Neuron Selectivity Transfer loss of one feature pair, f_s [B,Cs,Hs,Ws] and f_t [B,Ct,Ht,Wt] (float32 or bfloat16, contiguous
+    or channels_last, independently per side; at most 256 channels each) -> scalar float32:
+    mean_(b,i,j) Gss^2 - 2 mean_(b,i,j) Gst^2 with Gss / Gst the Gram of the L2-normalised channel rows of f_s with themselves / with
+    those of f_t.  Heights that differ: the larger map goes through stock adaptive_avg_pool2d to (h, h), h = min(Hs, Ht), in front
+    of the kernels (its autograd carries that part of the gradient).  The gradient flows to f_s only."""
+    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
+        _dev(t, nm, dtype=None, contiguous=False)
+        if t.dim() != 4:
+            raise ValueError(f"nst_loss: {nm} must be [B,C,H,W], got {tuple(t.shape)}")
+    if f_t.requires_grad and torch.is_grad_enabled():
+        raise ValueError("nst_loss: the kernels give no gradient to f_t (detach it, or use distiller_zoo.NSTLoss.composite)")
+    Hs, Ht = f_s.shape[2], f_t.shape[2]
+    if Hs > Ht:
+        f_s = torch.nn.functional.adaptive_avg_pool2d(f_s, (Ht, Ht))
+    elif Hs < Ht:
+        f_t = torch.nn.functional.adaptive_avg_pool2d(f_t, (Hs, Hs))
+    if f_s.shape[3] != f_t.shape[3]:
+        raise ValueError(f"nst_loss: widths {f_s.shape[3]} and {f_t.shape[3]} at height {min(Hs, Ht)}: the maps have no common grid")
+    return _NSTLoss.apply(f_s, f_t)

@@ -39,8 +39,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # the three hand-scheduled files (inline asm: checks a-d) and, for the spill budget (e) alone, the other kernel files of the KD path
 # (K3 / K4, the generic GEMM and the row kernels of the staged paths; the backbone helpers bn / dwconv / se can be named on the
 # command line: 600 more instantiations, all clean, a minute more); crd.hip is plain C++ (no inline asm): listed for (e) -- no spill
-# in its gather loops; attention.hip likewise (plain C++ streaming kernels): listed for (e)
-FILES = ["infonce_fused.hip", "infonce_f32.hip", "k1_fast.hip", "gemm.hip", "queue.hip", "rowops.hip", "crd.hip", "attention.hip"]
+# in its gather loops; attention.hip likewise (plain C++ streaming kernels): listed for (e); nst.hip (MFMA through the builtin, no
+# inline asm; 2 x 64 accumulator registers per lane): listed for (e)
+FILES = ["infonce_fused.hip", "infonce_f32.hip", "k1_fast.hip", "gemm.hip", "queue.hip", "rowops.hip", "crd.hip", "attention.hip",
+         "nst.hip"]
 SHOW = int(os.environ.get("AUDIT_SHOW", "3"))            # problems printed per kind and kernel
 
 # (e) kernels that may spill: demangled-name regex -> (max VGPR spills, max scratch bytes, max SGPR spills -- those go to the
