@@ -302,6 +302,38 @@ int moma_nst_bwd(const void* f_s, const void* f_t, const void* workspace, size_t
                  int dtype_t, int layout_t, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * RKD  Relational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
+ *      (distiller_zoo/RKD.py: pdist -> smooth L1 of the mean-normalised distances, and unsqueeze-difference -> F.normalize -> bmm ->
+ *      smooth L1 of the angles) and its autograd backward to f_s, without any [B, B, D] temporary.  For f_s [B, Ds], f_t [B, Dt]
+ *      (each side's feat[-1] flattened), per side S_ij = sum_k (x_ik - x_jk)^2, summed from the differences in double: exactly 0
+ *      on the diagonal and for equal rows, S_ij and S_ji the same bits.  Then
+ *          d_ij = sqrt(max(S_ij, 1e-12)) (0 for i = j)    mu = sum_ij d_ij / (B (B - 1))
+ *          l_d = (1/B^2) sum_ij sl1(d^s_ij / mu^s - d^t_ij / mu^t)        sl1(z) = z^2 / 2 for |z| < 1, |z| - 1/2 otherwise
+ *          n_ab = max(sqrt(S_ab), 1e-12)    A_a[b,c] = (S_ab + S_ac - S_bc) / (2 n_ab n_ac), 0 wherever S_ab = 0 or S_ac = 0
+ *          l_a = (1/B^3) sum_abc sl1(A^s_a[b,c] - A^t_a[b,c])             loss = w_d l_d + w_a l_a
+ *          Q_ij = d loss / d S^s_ij, the B^2 entries taken as independent (no gradient from d_ij where S_ij < 1e-12: the clamp)
+ *          dF_s = g_loss M (f_s - batch mean),  M = -2 (Q + Q^T) off the diagonal, each diagonal entry minus its row's other entries
+ *      A pair of EXACTLY equal student rows contributes value 0 and gradient 0 to the angle term (the reference's autograd divides
+ *      by F.normalize's clamp 1e-12 there and returns gradients of 1e10).  The gradient goes to f_s only.
+ *      f, f_s, dF_s: MOMA_DT_F32 or MOMA_DT_BF16, rows contiguous, aligned to their element size (16-byte loads where the base
+ *      address and D allow); S, Q and the workspace are double, 8-byte aligned; terms, loss and g_loss fp32.  All arithmetic in
+ *      double.  2 <= B <= MOMA_RKD_MAX_B (else MOMA_E_UNSUPPORTED, nothing is launched), any D >= 1.  No atomics: bitwise reproducible.
+ *
+ * workspace       moma_rkd_workspace_bytes(B) = (2 B^2 + 4 B + ceil(B / 16)^2) 8 bytes: 1 / n of both sides, four row sums per row and
+ *                 one partial sum per 16 x 16 tile; written and read by moma_rkd_terms alone.
+ * moma_rkd_dist   one side: f [B, D] -> S [B, B].  Call it once for f_s and once for f_t (Ds and Dt may differ).
+ * moma_rkd_terms  S_s, S_t -> Q [B, B], terms [2] = (l_d, l_a), loss [1].
+ * moma_rkd_bwd    f_s, Q -> dF_s [B, D] in f_s's dtype; g_loss is a DEVICE scalar (the upstream gradient of the loss, e.g. a GradScaler
+ *                 factor): nothing is read back to the host.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_RKD_MAX_B = 1024 };
+size_t moma_rkd_workspace_bytes(int B);
+int moma_rkd_dist(const void* f, int B, int D, int dtype, double* S, moma_stream_t stream);
+int moma_rkd_terms(const double* S_s, const double* S_t, int B, float w_d, float w_a, void* workspace, size_t workspace_bytes,
+                   double* Q, float* terms, float* loss, moma_stream_t stream);
+int moma_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF_s, int B, int D, int dtype, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1  batch-token multi-head attention -- replaces Attention.forward
  *     (MoMA/criterion_moco_att.py:153-167) and its autograd backward.
  *     x [N,d] -> qkv = x Wqkv^T + bqkv -> per head softmax(q k^T * hd^-1/2) v -> y = a Wproj^T + bproj.

@@ -769,4 +769,46 @@ int moma_nst_bwd(const void* f_s, const void* f_t, const void* workspace, size_t
                                  layout_t, (hipStream_t)stream));
 }
 
+// ---- Relational Knowledge Distillation ------------------------------------------------------------------------------------------
+static int rkd_check(int B, int D, int dtype) {
+    if (B <= 0 || D <= 0) return MOMA_E_SHAPE;
+    if (bad_dt(dtype)) return MOMA_E_DTYPE;
+    if (B < 2 || B > MOMA_RKD_MAX_B) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_rkd_workspace_bytes(int B) {
+    if (B < 2 || B > MOMA_RKD_MAX_B) return 0;
+    return rkd_workspace_bytes(B);
+}
+
+int moma_rkd_dist(const void* f, int B, int D, int dtype, double* S, moma_stream_t stream) {
+    if (!f || !S) return MOMA_E_NULL;
+    const int rc = rkd_check(B, D, dtype);
+    if (rc != MOMA_OK) return rc;
+    if (misaligned(f, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(S, 8)) return MOMA_E_ALIGN;
+    return hip_rc(launch_rkd_dist(f, B, D, dtype, S, (hipStream_t)stream));
+}
+
+int moma_rkd_terms(const double* S_s, const double* S_t, int B, float w_d, float w_a, void* workspace, size_t workspace_bytes,
+                   double* Q, float* terms, float* loss, moma_stream_t stream) {
+    if (!S_s || !S_t || !workspace || !Q || !terms || !loss) return MOMA_E_NULL;
+    const int rc = rkd_check(B, 1, MOMA_DT_F32);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < rkd_workspace_bytes(B)) return MOMA_E_WORKSPACE;
+    if (misaligned(S_s, 8) || misaligned(S_t, 8) || misaligned(workspace, 8) || misaligned(Q, 8) || misaligned(terms, 4) ||
+        misaligned(loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_rkd_terms(S_s, S_t, B, (double)w_d, (double)w_a, workspace, Q, terms, loss, (hipStream_t)stream));
+}
+
+int moma_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF_s, int B, int D, int dtype, moma_stream_t stream) {
+    if (!f_s || !Q || !g_loss || !dF_s) return MOMA_E_NULL;
+    const int rc = rkd_check(B, D, dtype);
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(Q, 8) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_rkd_bwd(f_s, Q, g_loss, dF_s, B, D, dtype, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -211,6 +211,14 @@ hipError_t launch_nst_gram(const void* fs, const void* ft, int B, int Cs, int Ct
 hipError_t launch_nst_bwd(const void* fs, const void* ft, const float* G, const float* norms, const float* rows, const float* g_loss,
                           void* dF, int B, int Cs, int Ct, int P, int dt_s, int lay_s, int dt_t, int lay_t, hipStream_t st);
 
+// ---- rkd.hip (Relational Knowledge Distillation: pairwise squared distances, the distance and angle terms, the student's gradient) --
+size_t rkd_workspace_bytes(int B);
+hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st);
+hipError_t launch_rkd_terms(const double* S_s, const double* S_t, int B, double w_d, double w_a, void* ws, double* Q, float* terms,
+                            float* loss, hipStream_t st);
+hipError_t launch_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF, int B, long long D, int dtype,
+                          hipStream_t st);
+
 // ---- infonce_fused.hip (one-pass flash-style kernel) ----------------------------------------------
 bool infonce_flash_supported(int B, int d, int K, int qdtype, int prec);
 size_t infonce_flash_workspace_bytes(int B, int d, int K);

@@ -1,5 +1,6 @@
 from .AT import Attention
 from .KD import DistillKL
 from .NST import NSTLoss
+from .RKD import RKDLoss
 
-__all__ = ["Attention", "DistillKL", "NSTLoss"]
+__all__ = ["Attention", "DistillKL", "NSTLoss", "RKDLoss"]

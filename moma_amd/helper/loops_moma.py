@@ -24,6 +24,11 @@ and so is the step.
 intermediate feature maps short of the last one, through the same teacher branch as `attention` (one eager no-grad forward with
 every feature map, dtype and memory format as the backbones left them: csrc/nst.hip reads fp32 / bf16 and NCHW / channels_last per
 side).  Nothing to train besides the student, no memory; the step is eager.
+
+`--distill rkd` (reference :155-158): the KD term is RKDLoss(feat_s[-1], feat_t[-1]) -- Relational Knowledge Distillation on the last
+feature of the student's forward and of the teacher's single no-grad forward (which rides detached in the key slot, in the dtype
+autocast left it: csrc/rkd.hip reads fp32 / bf16 per side and does its arithmetic in double).  Nothing to train besides the student, no
+memory; the step is eager.
 """
 from __future__ import print_function
 
@@ -122,6 +127,8 @@ class MomaStep:
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
             return lt.float(), ft[-1].float(), None
+        if opt.distill == "rkd":          # (:155-158) likewise, as autocast left it
+            return lt.float(), ft[-1].detach(), None
         if opt.distill != "moma":
             return lt.float(), None, None
         student = _unwrap(self.model_s)
@@ -175,6 +182,8 @@ class MomaStep:
             out["g_s"] = list(feat_s[1:-1])                                               # (:289)
         if opt.distill == "nst":
             out["g_s"] = list(feat_s[1:-2])                                               # (:151)
+        if opt.distill == "rkd":
+            f_s = feat_s[-1]                                                              # (:156)
         if opt.distill == "moma":
             with self.autocast():
                 f_s = criterion_kd.embed_s(feat_s[-1])                                    # (:323-324)
@@ -236,6 +245,8 @@ class MomaStep:
                 return criterion_kd(fw["f_s"], fw["k"], fw["index"], fw["contrast_idx"]).float()
         if opt.distill in ("attention", "nst"):                                           # (:287-292 / :150-154) g_t rides in fw["k"]
             return sum(criterion_kd(fw["g_s"], fw["k"])).float()
+        if opt.distill == "rkd":                                                          # (:155-158) f_t rides in fw["k"]
+            return criterion_kd(fw["f_s"], fw["k"]).float()
         if opt.distill != "moma":
             raise NotImplementedError(opt.distill)
         f_s, k, all_k, qp = fw["f_s"], fw["k"], fw["all_k"], fw["qp"]

@@ -1234,3 +1234,77 @@ def nst_loss(f_s, f_t) -> torch.Tensor:
     if f_s.shape[3] != f_t.shape[3]:
         raise ValueError(f"nst_loss: widths {f_s.shape[3]} and {f_t.shape[3]} at height {min(Hs, Ht)}: the maps have no common grid")
     return _NSTLoss.apply(f_s, f_t)
+
+
+# ------------------------------------------------------------------------------------------------
+# Relational Knowledge Distillation: pairwise distances and angles of a batch   (distiller_zoo/RKD.py, helper/loops_moma.py:155-158)
+# ------------------------------------------------------------------------------------------------
+def _rkd_side(f, name):
+    """-> [B, D] view of a contiguous [B, D] or [B, C, 1, 1] (any [B, ...]) float32 / bfloat16 device tensor (copied when not dense)"""
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() < 2 or f.dtype not in _DT_CODES:
+        raise TypeError(f"rkd_loss: {name} must be a float32 / bfloat16 tensor [B, ...], got {tuple(f.shape)} {f.dtype}")
+    return f.contiguous().view(f.shape[0], -1)
+
+
+class _RKDLoss(torch.autograd.Function):
+    """rkd_dist x 2 -> rkd_terms (Q = d loss / d S_s, loss) in the forward; rkd_bwd (dF_s from f_s and Q) in the backward."""
+
+    @staticmethod
+    def forward(ctx, f_s, f_t, w_d, w_a):
+        lib = _lib.load()
+        shape = f_s.shape
+        x, y = _rkd_side(f_s, "f_s"), _rkd_side(f_t, "f_t")
+        B, dev = x.shape[0], x.device
+        with _timed("moma_rkd_fwd"):
+            n = lib.moma_rkd_workspace_bytes(B)
+            if n == 0:
+                raise ValueError(f"rkd_loss: the kernels take 2 .. {_lib.RKD_MAX_B} rows, got {B}")
+            S = torch.empty(2, B, B, device=dev, dtype=torch.float64)
+            Q = torch.empty(B, B, device=dev, dtype=torch.float64)
+            ws = torch.empty(n // 8, device=dev, dtype=torch.float64)
+            terms = torch.empty(2, device=dev, dtype=torch.float32)
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            for side, t in enumerate((x, y)):
+                check(lib.moma_rkd_dist(_ptr(t), B, t.shape[1], _DT_CODES[t.dtype], _ptr(S[side]), _stream()), "moma_rkd_dist")
+            check(lib.moma_rkd_terms(_ptr(S[0]), _ptr(S[1]), B, float(w_d), float(w_a), _ptr(ws), n, _ptr(Q), _ptr(terms), _ptr(loss),
+                                     _stream()), "moma_rkd_terms")
+        # (rkd_loss, the only caller, refuses an f_t that wants a gradient: backward runs only where f_s does, with these saved)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, Q)
+        ctx.shape, ctx.strides = shape, f_s.stride()
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, Q = ctx.saved_tensors
+        B, D = x.shape
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        with _timed("moma_rkd_bwd"):
+            dF = torch.empty(ctx.shape, device=x.device, dtype=x.dtype)          # (contiguous, as the input the kernels saw)
+            if dF.stride() != ctx.strides:                                       # (extents of 1 may carry any stride: the input's)
+                dF = dF.as_strided(ctx.shape, ctx.strides)
+            check(lib.moma_rkd_bwd(_ptr(x), _ptr(Q), _ptr(g), _ptr(dF), B, D, _DT_CODES[x.dtype], _stream()), "moma_rkd_bwd")
+        return dF, None, None, None
+
+
+def rkd_loss(f_s, f_t, w_d=25.0, w_a=50.0) -> torch.Tensor:
+    """Relational Knowledge Distillation loss of one pair of feature batches, f_s [B, Ds] and f_t [B, Dt] (or [B, C, 1, 1]; float32
+    or bfloat16, contiguous, independently per side; 2 <= B <= 1024) -> scalar float32:
+    w_d * smooth_l1 of the mean-normalised pairwise distances + w_a * smooth_l1 of the angles at every anchor, both from the B x B
+    matrices of squared distances in double (no [B, B, D] temporary).  The gradient flows to f_s only."""
+    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
+        _dev(t, nm, dtype=None, contiguous=False)
+        if t.dim() < 2:
+            raise ValueError(f"rkd_loss: {nm} must be [B, D] or [B, C, 1, 1], got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"rkd_loss: {nm} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
+    if f_t.requires_grad and torch.is_grad_enabled():
+        raise ValueError("rkd_loss: the kernels give no gradient to f_t (detach it, or use distiller_zoo.RKDLoss.composite)")
+    if f_s.shape[0] != f_t.shape[0]:
+        raise ValueError(f"rkd_loss: batch sizes {f_s.shape[0]} and {f_t.shape[0]} differ")
+    if f_s.shape[0] < 2:
+        raise ValueError("rkd_loss: relations need at least two rows, got B = 1")
+    return _RKDLoss.apply(f_s, f_t, float(w_d), float(w_a))
