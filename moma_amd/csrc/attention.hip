@@ -220,8 +220,7 @@ __global__ __launch_bounds__(AT_THREADS) void at_bwd_nhwc_kernel(const T* __rest
 // ---- the pair ----------------------------------------------------------------------------------------------------------------------
 // sum over the workgroup's 256 threads in an order that depends on nothing but the thread index; result in every thread
 __device__ __forceinline__ double at_block_sum(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     const double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
@@ -285,12 +284,8 @@ __global__ __launch_bounds__(AT_THREADS) void at_loss_kernel(const float* __rest
 }
 
 // ---- plans (host) ----------------------------------------------------------------------------------------------------------------
-// widest vector the PV<> accessors offer for `n_div` contiguous elements at an address with the low bits `bits`
-int at_vec(long n_div, int elem_bytes, uintptr_t bits) {
-    for (int v = 16 / elem_bytes; v > 1; v >>= 1)
-        if (v != 2 && n_div % v == 0 && bits % (v * elem_bytes) == 0) return v;
-    return 1;
-}
+// 16 bytes / 4 elements / 1 (never 2) for `n_div` contiguous elements at an address with the low bits `bits`
+int at_pick(long n_div, int elem_bytes, uintptr_t bits) { return pick_vec(n_div, elem_bytes, bits, {16 / elem_bytes, 4}); }
 unsigned at_grid(long long items) {
     return (unsigned)(items < 1 ? 1 : (items > AT_MAX_BLOCKS ? AT_MAX_BLOCKS : items));
 }
@@ -321,19 +316,22 @@ size_t at_workspace_bytes(int B, int C, int H, int W, int oh, int ow, int layout
     return S == 1 ? 0 : (size_t)S * B * oh * ow * sizeof(float);
 }
 
-#define AT_NCHW_DISPATCH(KERNEL, T, MAXV, ...)                                                                              \
-    do {                                                                                                                    \
-        if (pool) hipLaunchKernelGGL((KERNEL<T, 1, true>), grid, dim3(AT_THREADS), 0, st, __VA_ARGS__);                    \
-        else if (MAXV == 8 && vec == 8) hipLaunchKernelGGL((KERNEL<T, MAXV, false>), grid, dim3(AT_THREADS), 0, st, __VA_ARGS__); \
-        else if (vec >= 4) hipLaunchKernelGGL((KERNEL<T, 4, false>), grid, dim3(AT_THREADS), 0, st, __VA_ARGS__);          \
-        else hipLaunchKernelGGL((KERNEL<T, 1, false>), grid, dim3(AT_THREADS), 0, st, __VA_ARGS__);                        \
-    } while (0)
-#define AT_NHWC_DISPATCH(KERNEL, T, MAXV, ...)                                                                              \
-    do {                                                                                                                    \
-        if (MAXV == 8 && vec == 8) hipLaunchKernelGGL((KERNEL<T, MAXV>), grid, dim3(AT_THREADS), 0, st, __VA_ARGS__);      \
-        else if (vec >= 4) hipLaunchKernelGGL((KERNEL<T, 4>), grid, dim3(AT_THREADS), 0, st, __VA_ARGS__);                 \
-        else hipLaunchKernelGGL((KERNEL<T, 1>), grid, dim3(AT_THREADS), 0, st, __VA_ARGS__);                               \
-    } while (0)
+// launch NCHW<T, V, POOL> (the pooling kernels are scalar) or NHWC<T, V> for the run-time (dtype, vec): f(kernel type tag, V[, POOL])
+template <typename F> void at_nchw_dispatch(int dtype, bool pool, int vec, F&& f) {
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (pool) f(t, std::integral_constant<int, 1>{}, std::true_type{});
+        else with_vec<MAXVEC<T>, 8, 4, 1>(vec, [&](auto V) { f(t, V, std::false_type{}); });
+        return 0;
+    });
+}
+template <typename F> void at_nhwc_dispatch(int dtype, int vec, F&& f) {
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_vec<MAXVEC<T>, 8, 4, 1>(vec, [&](auto V) { f(t, V); });
+        return 0;
+    });
+}
 
 hipError_t launch_at_map(const void* f, float* a, int B, int C, int H, int W, int oh, int ow, int dtype, int layout, void* ws,
                          hipStream_t st) {
@@ -343,7 +341,7 @@ hipError_t launch_at_map(const void* f, float* a, int B, int C, int H, int W, in
     const long long ohw = (long long)oh * ow;
     const float inv_C = (float)(1.0 / (double)C);
     if (layout == MOMA_LAYOUT_NCHW) {
-        const int vec = pool ? 1 : at_vec((long)ohw, eb, (uintptr_t)f);
+        const int vec = pool ? 1 : at_pick((long)ohw, eb, (uintptr_t)f);
         const int tiles = (int)((ohw + 64LL * vec - 1) / (64LL * vec));
         const int S = at_map_splits(q);
         const int cps = (C + S - 1) / S;
@@ -351,8 +349,11 @@ hipError_t launch_at_map(const void* f, float* a, int B, int C, int H, int W, in
         float* out = S == 1 ? a : (float*)ws;
         const float scale = S == 1 ? inv_C : 1.f;
         const dim3 grid(at_grid(items));
-        if (dtype == MOMA_DT_BF16) AT_NCHW_DISPATCH(at_map_nchw_kernel, bf16_raw, 8, (const bf16_raw*)f, out, q, tiles, S, cps, scale, items);
-        else AT_NCHW_DISPATCH(at_map_nchw_kernel, float, 4, (const float*)f, out, q, tiles, S, cps, scale, items);
+        at_nchw_dispatch(dtype, pool, vec, [&](auto t, auto V, auto POOL) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((at_map_nchw_kernel<T, V, POOL>), grid, dim3(AT_THREADS), 0, st, (const T*)f, out, q, tiles, S, cps, scale,
+                               items);
+        });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || S == 1) return e;
         const long long n = (long long)B * ohw;
@@ -360,13 +361,15 @@ hipError_t launch_at_map(const void* f, float* a, int B, int C, int H, int W, in
                            (const float*)ws, a, S, n, inv_C);
         return hipGetLastError();
     }
-    const int vec = at_vec(C, eb, (uintptr_t)f);
+    const int vec = at_pick(C, eb, (uintptr_t)f);
     const int lpp_log2 = at_lpp_log2(C / vec);
     const long long npix = (long long)B * ohw;
     const long long ppb = (long long)AT_WAVES * (64 >> lpp_log2);
     const dim3 grid(at_grid((npix + ppb - 1) / ppb));
-    if (dtype == MOMA_DT_BF16) AT_NHWC_DISPATCH(at_map_nhwc_kernel, bf16_raw, 8, (const bf16_raw*)f, a, q, lpp_log2, inv_C, npix);
-    else AT_NHWC_DISPATCH(at_map_nhwc_kernel, float, 4, (const float*)f, a, q, lpp_log2, inv_C, npix);
+    at_nhwc_dispatch(dtype, vec, [&](auto t, auto V) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((at_map_nhwc_kernel<T, V>), grid, dim3(AT_THREADS), 0, st, (const T*)f, a, q, lpp_log2, inv_C, npix);
+    });
     return hipGetLastError();
 }
 
@@ -389,7 +392,7 @@ hipError_t launch_at_bwd(const void* f, const float* g_a, const float* g_loss, v
     const float k = (float)(2.0 / ((double)C * q.rh * q.rw));
     const uintptr_t bits = (uintptr_t)f | (uintptr_t)dF;
     if (layout == MOMA_LAYOUT_NCHW) {
-        const int vec = pool ? 1 : at_vec((long)ohw, eb, bits);
+        const int vec = pool ? 1 : at_pick((long)ohw, eb, bits);
         const int tiles = (int)((ohw + 64LL * vec - 1) / (64LL * vec));
         // about 2048 workgroups over (b, tile, channel chunk), every wave of a chunk with a channel of its own where C allows
         const long long items0 = (long long)B * tiles;
@@ -400,19 +403,22 @@ hipError_t launch_at_bwd(const void* f, const float* g_a, const float* g_loss, v
         nchunk = (C + cpc - 1) / cpc;
         const long long items = items0 * nchunk;
         const dim3 grid(at_grid(items));
-        if (dtype == MOMA_DT_BF16)
-            AT_NCHW_DISPATCH(at_bwd_nchw_kernel, bf16_raw, 8, (const bf16_raw*)f, g_a, g_loss, (bf16_raw*)dF, q, tiles, (int)nchunk, cpc, k, items);
-        else
-            AT_NCHW_DISPATCH(at_bwd_nchw_kernel, float, 4, (const float*)f, g_a, g_loss, (float*)dF, q, tiles, (int)nchunk, cpc, k, items);
+        at_nchw_dispatch(dtype, pool, vec, [&](auto t, auto V, auto POOL) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((at_bwd_nchw_kernel<T, V, POOL>), grid, dim3(AT_THREADS), 0, st, (const T*)f, g_a, g_loss, (T*)dF, q, tiles,
+                               (int)nchunk, cpc, k, items);
+        });
         return hipGetLastError();
     }
-    const int vec = at_vec(C, eb, bits);
+    const int vec = at_pick(C, eb, bits);
     const int lpp_log2 = at_lpp_log2(C / vec);
     const long long npix = (long long)B * ohw;
     const long long ppb = (long long)AT_WAVES * (64 >> lpp_log2);
     const dim3 grid(at_grid((npix + ppb - 1) / ppb));
-    if (dtype == MOMA_DT_BF16) AT_NHWC_DISPATCH(at_bwd_nhwc_kernel, bf16_raw, 8, (const bf16_raw*)f, g_a, g_loss, (bf16_raw*)dF, q, lpp_log2, k, npix);
-    else AT_NHWC_DISPATCH(at_bwd_nhwc_kernel, float, 4, (const float*)f, g_a, g_loss, (float*)dF, q, lpp_log2, k, npix);
+    at_nhwc_dispatch(dtype, vec, [&](auto t, auto V) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((at_bwd_nhwc_kernel<T, V>), grid, dim3(AT_THREADS), 0, st, (const T*)f, g_a, g_loss, (T*)dF, q, lpp_log2, k, npix);
+    });
     return hipGetLastError();
 }
 

@@ -22,70 +22,6 @@ namespace {
 
 constexpr int BN_THREADS = 256;
 
-template <typename T, int VEC>
-struct VecIO;
-template <int VEC>
-struct VecIO<float, VEC> {
-    __device__ static void load(const float* p, float (&v)[VEC]) {
-        if constexpr (VEC == 8) {
-            const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        } else if constexpr (VEC == 4) {
-            const float4 a = *reinterpret_cast<const float4*>(p);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        } else {
-            v[0] = *p;
-        }
-    }
-    __device__ static void store(float* p, const float (&v)[VEC]) {
-        if constexpr (VEC == 8) {
-            *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-            *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        } else if constexpr (VEC == 4) {
-            *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-            *p = v[0];
-        }
-    }
-};
-template <int VEC>
-struct VecIO<bf16_raw, VEC> {
-    __device__ static void load(const bf16_raw* p, float (&v)[VEC]) {
-        if constexpr (VEC == 8) {
-            const uint4 a = *reinterpret_cast<const uint4*>(p);
-            const unsigned w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v[2 * i] = __uint_as_float(w[i] << 16);
-                v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-            }
-        } else if constexpr (VEC == 4) {
-            const uint2 a = *reinterpret_cast<const uint2*>(p);
-            v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
-            v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
-        } else {
-            v[0] = bf16_to_f32(*p);
-        }
-    }
-    __device__ static void store(bf16_raw* p, const float (&v)[VEC]) {
-        if constexpr (VEC == 8) {
-            uint4 a;
-            a.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-            a.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-            a.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-            a.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
-            *reinterpret_cast<uint4*>(p) = a;
-        } else if constexpr (VEC == 4) {
-            uint2 a;
-            a.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-            a.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-            *reinterpret_cast<uint2*>(p) = a;
-        } else {
-            *p = f32_to_bf16(v[0]);
-        }
-    }
-};
-
 // (act_fwd: common.hpp)
 // d act(y) / dy
 __device__ __forceinline__ float act_grad(float y, int act) {
@@ -119,7 +55,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const T* __restric
     for (unsigned i = s * BN_THREADS + threadIdx.x; i < total; i += S * BN_THREADS) {
         const unsigned n = i / hwv, r = i - n * hwv;
         float v[VEC];
-        VecIO<T, VEC>::load(x + ((size_t)n * C + c) * HW + (size_t)r * VEC, v);
+        PV<T, VEC>::ld(x + ((size_t)n * C + c) * HW + (size_t)r * VEC, v);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             sum += v[j];
@@ -205,10 +141,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T* __restric
         const unsigned plane = (unsigned)(i / hwv), c = plane % (unsigned)C;
         const float sc = scale_shift[2 * c], sh = scale_shift[2 * c + 1];
         float v[VEC];
-        VecIO<T, VEC>::load(x + i * VEC, v);
+        PV<T, VEC>::ld(x + i * VEC, v);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) v[j] = act_fwd(fmaf(v[j], sc, sh), act);
-        VecIO<T, VEC>::store(out + i * VEC, v);
+        PV<T, VEC>::st(out + i * VEC, v);
     }
 }
 
@@ -229,18 +165,18 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_mean_kernel(const T* __re
         float acc = 0.f;
         for (int i = lane; i < nv; i += 64) {
             float v[VEC];
-            VecIO<T, VEC>::load(p + (size_t)i * VEC, v);
+            PV<T, VEC>::ld(p + (size_t)i * VEC, v);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 v[j] = act_fwd(fmaf(v[j], sc, sh), act);
                 acc += v[j];
             }
-            VecIO<T, VEC>::store(o + (size_t)i * VEC, v);
+            PV<T, VEC>::st(o + (size_t)i * VEC, v);
         }
         acc = wave_sum(acc);
         if (lane == 0) {
             float m[1] = {acc / (float)HW};
-            VecIO<T, 1>::store(pmean + plane, m);
+            PV<T, 1>::st(pmean + plane, m);
         }
     }
 }
@@ -266,10 +202,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_reduce_kernel(const T* __re
         const unsigned n = i / hwv, r = i - n * hwv;
         const size_t off = ((size_t)n * C + c) * HW + (size_t)r * VEC;
         float xv[VEC], dv[VEC];
-        VecIO<T, VEC>::load(x + off, xv);
-        VecIO<T, VEC>::load(dout + off, dv);
+        PV<T, VEC>::ld(x + off, xv);
+        PV<T, VEC>::ld(dout + off, dv);
         float add = 0.f;
-        if (dpl) { float t1[1]; VecIO<T, 1>::load(dpl + (size_t)n * C + c, t1); add = t1[0] * inv_hw; }
+        if (dpl) { float t1[1]; PV<T, 1>::ld(dpl + (size_t)n * C + c, t1); add = t1[0] * inv_hw; }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             const float xh = (xv[j] - mean) * invstd;
@@ -331,25 +267,23 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const T* __res
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
         const float a = coef[3 * c], b1 = coef[3 * c + 1], b2 = coef[3 * c + 2];
         float xv[VEC], dv[VEC];
-        VecIO<T, VEC>::load(x + i * VEC, xv);
-        VecIO<T, VEC>::load(dout + i * VEC, dv);
+        PV<T, VEC>::ld(x + i * VEC, xv);
+        PV<T, VEC>::ld(dout + i * VEC, dv);
         float add = 0.f;
-        if (dpl) { float t1[1]; VecIO<T, 1>::load(dpl + plane, t1); add = t1[0] * inv_hw; }
+        if (dpl) { float t1[1]; PV<T, 1>::ld(dpl + plane, t1); add = t1[0] * inv_hw; }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             const float xh = (xv[j] - mean) * invstd;
             const float dy = (dv[j] + add) * act_grad(fmaf(xh, g, b), act);
             xv[j] = a * (dy - b1 - xh * b2);
         }
-        VecIO<T, VEC>::store(dx + i * VEC, xv);
+        PV<T, VEC>::st(dx + i * VEC, xv);
     }
 }
 
-int pick_vec(int HW, int elem_bytes, const void* a, const void* b, const void* c) {
-    const uintptr_t bits = (uintptr_t)a | (uintptr_t)b | (uintptr_t)c;
-    if (HW % 8 == 0 && bits % (8 * elem_bytes) == 0) return 8;
-    if (HW % 4 == 0 && bits % (4 * elem_bytes) == 0) return 4;
-    return 1;
+// 8 / 4 / 1 elements of either type (fp32 at 8: two 16-byte accesses, 32-byte aligned)
+int bn_vec(int HW, int elem_bytes, const void* a, const void* b, const void* c) {
+    return pick_vec(HW, elem_bytes, (uintptr_t)a | (uintptr_t)b | (uintptr_t)c, {8, 4});
 }
 int pick_splits(int N, int C, int HW, int vec) {
     const long per_channel = (long)N * (HW / vec);
@@ -376,9 +310,9 @@ void bn_prepare_t(const T* x, const float* gamma, const float* beta, float* rm, 
     const int S = training ? pick_splits(N, C, HW, vec) : 1;
     if (training) {
         dim3 grid(S, C);
-        if (vec == 8) hipLaunchKernelGGL((bn_stats_kernel<T, 8>), grid, dim3(BN_THREADS), 0, st, x, partial, N, C, HW);
-        else if (vec == 4) hipLaunchKernelGGL((bn_stats_kernel<T, 4>), grid, dim3(BN_THREADS), 0, st, x, partial, N, C, HW);
-        else hipLaunchKernelGGL((bn_stats_kernel<T, 1>), grid, dim3(BN_THREADS), 0, st, x, partial, N, C, HW);
+        with_vec<8, 8, 4, 1>(vec, [&](auto V) {
+            hipLaunchKernelGGL((bn_stats_kernel<T, V>), grid, dim3(BN_THREADS), 0, st, x, partial, N, C, HW);
+        });
     }
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, partial, S, gamma, beta, rm, rv,
                        save_mean, save_invstd, scale_shift, C, training, momentum, eps);
@@ -388,7 +322,7 @@ template <typename T>
 hipError_t bn_fwd_t(const T* x, T* out, const float* gamma, const float* beta, float* rm, float* rv, float* save_mean,
                     float* save_invstd, float* ws, int N, int C, int HW, int act, int training, float momentum,
                     float eps, T* pmean, hipStream_t st) {
-    const int vec = pick_vec(HW, sizeof(T), x, out, nullptr);
+    const int vec = bn_vec(HW, sizeof(T), x, out, nullptr);
     float* scale_shift = ws;                   // [C][2]
     float* partial = ws + 2 * (size_t)C;       // [C][S][3]
     const size_t nvec = (size_t)N * C * HW / vec;
@@ -398,15 +332,16 @@ hipError_t bn_fwd_t(const T* x, T* out, const float* gamma, const float* beta, f
         long gp = ((long)N * C + BN_THREADS / 64 - 1) / (BN_THREADS / 64);
         if (gp > 256 * 32) gp = 256 * 32;
         const dim3 pg((unsigned)gp);
-        if (vec == 8) hipLaunchKernelGGL((bn_apply_mean_kernel<T, 8>), pg, dim3(BN_THREADS), 0, st, x, out, pmean, scale_shift, N * C, C, HW, act);
-        else if (vec == 4) hipLaunchKernelGGL((bn_apply_mean_kernel<T, 4>), pg, dim3(BN_THREADS), 0, st, x, out, pmean, scale_shift, N * C, C, HW, act);
-        else hipLaunchKernelGGL((bn_apply_mean_kernel<T, 1>), pg, dim3(BN_THREADS), 0, st, x, out, pmean, scale_shift, N * C, C, HW, act);
+        with_vec<8, 8, 4, 1>(vec, [&](auto V) {
+            hipLaunchKernelGGL((bn_apply_mean_kernel<T, V>), pg, dim3(BN_THREADS), 0, st, x, out, pmean, scale_shift, N * C, C, HW,
+                               act);
+        });
         return hipGetLastError();
     }
     const unsigned g = apply_grid(nvec);
-    if (vec == 8) hipLaunchKernelGGL((bn_apply_kernel<T, 8>), dim3(g), dim3(BN_THREADS), 0, st, x, out, scale_shift, C, HW, nvec, act);
-    else if (vec == 4) hipLaunchKernelGGL((bn_apply_kernel<T, 4>), dim3(g), dim3(BN_THREADS), 0, st, x, out, scale_shift, C, HW, nvec, act);
-    else hipLaunchKernelGGL((bn_apply_kernel<T, 1>), dim3(g), dim3(BN_THREADS), 0, st, x, out, scale_shift, C, HW, nvec, act);
+    with_vec<8, 8, 4, 1>(vec, [&](auto V) {
+        hipLaunchKernelGGL((bn_apply_kernel<T, V>), dim3(g), dim3(BN_THREADS), 0, st, x, out, scale_shift, C, HW, nvec, act);
+    });
     return hipGetLastError();
 }
 
@@ -414,22 +349,24 @@ template <typename T>
 hipError_t bn_bwd_t(const T* x, const T* dout, const float* gamma, const float* beta, const float* save_mean,
                     const float* save_invstd, T* dx, float* dgamma, float* dbeta, float* ws, int N, int C, int HW,
                     int act, int training, const T* dpl, hipStream_t st) {
-    const int vec = pick_vec(HW, sizeof(T), x, dout, dx);
+    const int vec = bn_vec(HW, sizeof(T), x, dout, dx);
     const int S = pick_splits(N, C, HW, vec);
     float* coef = ws;                          // [C][3]
     float* partial = ws + 3 * (size_t)C;       // [C][S][2]
     const size_t nvec = (size_t)N * C * HW / vec;
     dim3 grid(S, C);
-    if (vec == 8) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 8>), grid, dim3(BN_THREADS), 0, st, x, dout, gamma, beta, save_mean, save_invstd, partial, N, C, HW, act, dpl);
-    else if (vec == 4) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 4>), grid, dim3(BN_THREADS), 0, st, x, dout, gamma, beta, save_mean, save_invstd, partial, N, C, HW, act, dpl);
-    else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 1>), grid, dim3(BN_THREADS), 0, st, x, dout, gamma, beta, save_mean, save_invstd, partial, N, C, HW, act, dpl);
+    with_vec<8, 8, 4, 1>(vec, [&](auto V) {
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, V>), grid, dim3(BN_THREADS), 0, st, x, dout, gamma, beta, save_mean,
+                           save_invstd, partial, N, C, HW, act, dpl);
+    });
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, partial, S, gamma, save_invstd,
                        dgamma, dbeta, coef, C, (float)N * (float)HW, training);
     if (dx) {
         const unsigned g = apply_grid(nvec);
-        if (vec == 8) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 8>), dim3(g), dim3(BN_THREADS), 0, st, x, dout, dx, gamma, beta, save_mean, save_invstd, coef, C, HW, nvec, act, dpl);
-        else if (vec == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 4>), dim3(g), dim3(BN_THREADS), 0, st, x, dout, dx, gamma, beta, save_mean, save_invstd, coef, C, HW, nvec, act, dpl);
-        else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 1>), dim3(g), dim3(BN_THREADS), 0, st, x, dout, dx, gamma, beta, save_mean, save_invstd, coef, C, HW, nvec, act, dpl);
+        with_vec<8, 8, 4, 1>(vec, [&](auto V) {
+            hipLaunchKernelGGL((bn_bwd_apply_kernel<T, V>), dim3(g), dim3(BN_THREADS), 0, st, x, dout, dx, gamma, beta, save_mean,
+                               save_invstd, coef, C, HW, nvec, act, dpl);
+        });
     }
     return hipGetLastError();
 }
@@ -440,11 +377,11 @@ size_t bn_workspace_floats(int C) { return (size_t)C * (3 + 64 * 3); }
 hipError_t launch_bn_fwd(const void* x, void* out, const float* gamma, const float* beta, float* rm, float* rv,
                          float* save_mean, float* save_invstd, float* ws, int N, int C, int HW, int dtype, int act,
                          int training, float momentum, float eps, void* plane_mean, hipStream_t st) {
-    if (dtype == MOMA_DT_BF16)
-        return bn_fwd_t<bf16_raw>((const bf16_raw*)x, (bf16_raw*)out, gamma, beta, rm, rv, save_mean, save_invstd, ws, N,
-                                  C, HW, act, training, momentum, eps, (bf16_raw*)plane_mean, st);
-    return bn_fwd_t<float>((const float*)x, (float*)out, gamma, beta, rm, rv, save_mean, save_invstd, ws, N, C, HW, act,
-                           training, momentum, eps, (float*)plane_mean, st);
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return bn_fwd_t<T>((const T*)x, (T*)out, gamma, beta, rm, rv, save_mean, save_invstd, ws, N, C, HW, act, training, momentum,
+                           eps, (T*)plane_mean, st);
+    });
 }
 // the forward without its apply pass: what launch_bn_fwd computes ahead of it, for a consumer that applies scale / shift itself
 // (same kernels, split count and merge order: x's own alignment picks the vector width, as it does next to an aligned `out`)
@@ -452,22 +389,21 @@ hipError_t launch_bn_prepare(const void* x, const float* gamma, const float* bet
                              float* save_invstd, float* scale_shift, float* ws, int N, int C, int HW, int dtype, int training,
                              float momentum, float eps, hipStream_t st) {
     float* partial = ws + 2 * (size_t)C;
-    if (dtype == MOMA_DT_BF16)
-        bn_prepare_t<bf16_raw>((const bf16_raw*)x, gamma, beta, rm, rv, save_mean, save_invstd, scale_shift, partial, N, C, HW,
-                               pick_vec(HW, sizeof(bf16_raw), x, nullptr, nullptr), training, momentum, eps, st);
-    else
-        bn_prepare_t<float>((const float*)x, gamma, beta, rm, rv, save_mean, save_invstd, scale_shift, partial, N, C, HW,
-                            pick_vec(HW, sizeof(float), x, nullptr, nullptr), training, momentum, eps, st);
-    return hipGetLastError();
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        bn_prepare_t<T>((const T*)x, gamma, beta, rm, rv, save_mean, save_invstd, scale_shift, partial, N, C, HW,
+                        bn_vec(HW, sizeof(T), x, nullptr, nullptr), training, momentum, eps, st);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_bn_bwd(const void* x, const void* dout, const float* gamma, const float* beta, const float* save_mean,
                          const float* save_invstd, void* dx, float* dgamma, float* dbeta, float* ws, int N, int C, int HW,
                          int dtype, int act, int training, const void* dplane_mean, hipStream_t st) {
-    if (dtype == MOMA_DT_BF16)
-        return bn_bwd_t<bf16_raw>((const bf16_raw*)x, (const bf16_raw*)dout, gamma, beta, save_mean, save_invstd,
-                                  (bf16_raw*)dx, dgamma, dbeta, ws, N, C, HW, act, training, (const bf16_raw*)dplane_mean, st);
-    return bn_bwd_t<float>((const float*)x, (const float*)dout, gamma, beta, save_mean, save_invstd, (float*)dx, dgamma,
-                           dbeta, ws, N, C, HW, act, training, (const float*)dplane_mean, st);
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return bn_bwd_t<T>((const T*)x, (const T*)dout, gamma, beta, save_mean, save_invstd, (T*)dx, dgamma, dbeta, ws, N, C, HW, act,
+                           training, (const T*)dplane_mean, st);
+    });
 }
 
 }  // namespace moma

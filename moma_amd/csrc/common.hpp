@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
+#include <type_traits>
 #include "../../include/moma_hip.h"
 
 namespace moma {
@@ -85,13 +87,42 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
-// ---- typed vector access of the streaming kernels (se.hip, attention.hip): VEC elements of storage type T <-> fp32, one
-//      memory instruction of up to 16 bytes; the pointer must be aligned to VEC elements -----------------------------
+// double -> float as a rounding of its own: written as a plain cast in front of a bf16 store the compiler merges the two roundings
+// into one double -> bf16 conversion, and a value that is a tie in fp32 then lands on the other side of what the fp32 output rounds to
+__device__ __forceinline__ float round_f32(double d) {
+    float f = (float)d;
+    asm("" : "+v"(f));
+    return f;
+}
+
+// ---- typed vector access: VEC elements of storage type T (float or bf16_raw) <-> fp32 registers, one memory instruction of up to
+//      16 bytes (PV<float, 8>: two); the pointer must be aligned to VEC elements.  THE accessor of every kernel file but the
+//      InfoNCE / K1 ones, which have operand layouts of their own --------------------------------------------------------------
+template <typename T> constexpr int MAXVEC = 16 / sizeof(T);        // elements of T in 16 bytes
 template <typename T, int VEC> struct PV;
+template <> struct PV<float, 8> {
+    static __device__ void ld(const float* p, float* v) {
+        const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    }
+    static __device__ void st(float* p, const float* v) {
+        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
+};
 template <> struct PV<float, 4> {
     static __device__ void ld(const float* p, float* v) { const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
     static __device__ void st(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <> struct PV<float, 2> {
+    static __device__ void ld(const float* p, float* v) { const float2 a = *reinterpret_cast<const float2*>(p); v[0] = a.x; v[1] = a.y; }
+    static __device__ void st(float* p, const float* v) { *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]); }
 };
 template <> struct PV<float, 1> {
     static __device__ void ld(const float* p, float* v) { v[0] = *p; }
@@ -126,12 +157,52 @@ template <> struct PV<bf16_raw, 4> {
         *reinterpret_cast<uint2*>(p) = a;
     }
 };
+template <> struct PV<bf16_raw, 2> {          // (load only: no kernel stores two bf16)
+    static __device__ void ld(const bf16_raw* p, float* v) {
+        const unsigned a = *reinterpret_cast<const unsigned*>(p);
+        v[0] = __uint_as_float(a << 16); v[1] = __uint_as_float(a & 0xffff0000u);
+    }
+};
 template <> struct PV<bf16_raw, 1> {
     static __device__ void ld(const bf16_raw* p, float* v) { v[0] = bf16_to_f32(*p); }
     static __device__ void st(bf16_raw* p, const float* v) { *p = f32_to_bf16(v[0]); }
 };
 template <typename T> __device__ __forceinline__ float ld1(const T* p) { float v; PV<T, 1>::ld(p, &v); return v; }
 template <typename T> __device__ __forceinline__ void st1(T* p, float v) { PV<T, 1>::st(p, &v); }
+
+// ---- the vector width of a launch (host) ------------------------------------------------------------------------------------
+// The first of `widths` (widest first) that divides `extent`, the run of contiguous elements, and whose byte size divides
+// `low_bits`, the OR of the addresses accessed at that width; else 1.  Every kernel family passes a list of its own, ON PURPOSE:
+// the width decides which elements one thread adds up, so it fixes the summation order of that family's reductions and with it
+// the bits of the results.  The static_asserts state what tells the lists apart.
+constexpr int pick_vec(long extent, int elem_bytes, uintptr_t low_bits, std::initializer_list<int> widths) {
+    for (const int v : widths)
+        if (extent % v == 0 && low_bits % (uintptr_t)(v * elem_bytes) == 0) return v;
+    return 1;
+}
+// bn.hip {8, 4} for both types: fp32 at 8 is two 16-byte accesses and asks for 32-byte alignment
+static_assert(pick_vec(56 * 56, 4, 0x20, {8, 4}) == 8 && pick_vec(56 * 56, 4, 0x10, {8, 4}) == 4, "bn");
+// se.hip, attention.hip {16 / eb, 4}: never 2
+static_assert(pick_vec(6, 2, 0, {8, 4}) == 1 && pick_vec(8, 4, 0, {4, 4}) == 4, "se / at");
+// dwconv.hip {16 / eb, 4, 2}: every power of two down to 2
+static_assert(pick_vec(6, 2, 0, {8, 4, 2}) == 2 && pick_vec(112, 2, 4, {8, 4, 2}) == 2, "dw");
+// nst.hip, rkd.hip {16 / eb}: 16 bytes or nothing
+static_assert(pick_vec(12, 2, 0, {8}) == 1 && pick_vec(16, 2, 0, {8}) == 8 && pick_vec(16, 2, 8, {8}) == 1, "nst / rkd");
+
+// ---- run-time (dtype, vec) -> template arguments (host) ----------------------------------------------------------------------
+// f(TypeTag<bf16_raw>{}) or f(TypeTag<float>{}) by MOMA_DT_*; inside a generic lambda: using T = typename decltype(t)::type
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> auto with_dtype(int dtype, F&& f) {
+    return dtype == MOMA_DT_BF16 ? f(TypeTag<bf16_raw>{}) : f(TypeTag<float>{});
+}
+// f(std::integral_constant<int, V>{}) for the V of the list V, REST... (widest first) that equals `vec`, the last one for any other
+// `vec`.  Widths above CAP (at most call sites MAXVEC<T>) are left out of the list: they get no instantiation.
+template <int CAP, int V, int... REST, typename F> void with_vec(int vec, F&& f) {
+    if constexpr (V > CAP) with_vec<CAP, REST...>(vec, f);
+    else if constexpr (sizeof...(REST) == 0) f(std::integral_constant<int, V>{});
+    else if (vec == V) f(std::integral_constant<int, V>{});
+    else with_vec<CAP, REST...>(vec, f);
+}
 
 // ---- generic batched GEMM:  C[m,n] (+)= alpha * sum_k A(m,k) * B(n,k) + bias[n] ----------------
 //   A(m,k) = transA ? A[k*lda + m] : A[m*lda + k]      (fp32)

@@ -47,11 +47,6 @@ __device__ __forceinline__ float group_sum(float v) {      // sum over the LPR l
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // grid (ceil(nchunk / 4), B, 2 sides), 256 threads = 4 waves, one chunk of j each
 template <int LPR, int VPL, int U, int MODE>
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(256) void crd_gather_kernel(const CrdArgs a) {
 
     const int64_t slot = ((int64_t)side * a.B + b) * a.nchunk + chunk;
     if (MODE == CRD_STATS || MODE == CRD_FUSED) {
-        const double t = wave_sum_f64(l == 0 ? lsum : 0.0);        // every lane of a row group holds the same sum: count it once
+        const double t = wave_sum(l == 0 ? lsum : 0.0);        // every lane of a row group holds the same sum: count it once
         if (lane == 0) a.part_sum[slot] = t;
     }
     if ((MODE == CRD_FUSED && a.want_dv) || MODE == CRD_SBWD) {

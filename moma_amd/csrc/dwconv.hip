@@ -28,49 +28,6 @@ constexpr int DW_WAVES = 4;                      // waves per workgroup, each wi
 constexpr int XO = 4;                            // tile column of image column 0 (16-B aligned, >= max left halo)
 constexpr int LDS_BUDGET = 64 * 1024;            // dynamic LDS per workgroup
 
-template <typename T, int VEC> struct Vec;
-template <> struct Vec<float, 4> { static __device__ void ld(const float* p, float* v) { const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; } };
-template <> struct Vec<float, 2> { static __device__ void ld(const float* p, float* v) { const float2 a = *reinterpret_cast<const float2*>(p); v[0] = a.x; v[1] = a.y; } };
-template <> struct Vec<float, 1> { static __device__ void ld(const float* p, float* v) { v[0] = *p; } };
-template <> struct Vec<bf16_raw, 8> {
-    static __device__ void ld(const bf16_raw* p, float* v) {
-        const uint4 a = *reinterpret_cast<const uint4*>(p);
-        const unsigned w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-    }
-};
-template <> struct Vec<bf16_raw, 4> {
-    static __device__ void ld(const bf16_raw* p, float* v) {
-        const uint2 a = *reinterpret_cast<const uint2*>(p);
-        v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
-        v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
-    }
-};
-template <> struct Vec<bf16_raw, 2> {
-    static __device__ void ld(const bf16_raw* p, float* v) {
-        const unsigned a = *reinterpret_cast<const unsigned*>(p);
-        v[0] = __uint_as_float(a << 16); v[1] = __uint_as_float(a & 0xffff0000u);
-    }
-};
-template <> struct Vec<bf16_raw, 1> { static __device__ void ld(const bf16_raw* p, float* v) { v[0] = bf16_to_f32(*p); } };
-
-template <int VEC> __device__ __forceinline__ void lds_store(float* p, const float* v) {
-    if constexpr (VEC == 8) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    } else if constexpr (VEC == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else if constexpr (VEC == 2) {
-        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-    } else {
-        *p = v[0];
-    }
-}
-template <typename T> __device__ __forceinline__ void st(T* p, float v);
-template <> __device__ __forceinline__ void st<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void st<bf16_raw>(bf16_raw* p, float v) { *p = f32_to_bf16(v); }
-
 struct DwShape {
     int NC, C, H, W, OH, OW, pt, pl;             // planes, channels, source / result plane sizes, top / left padding
     int TH, nbands, PB, ngroups;                 // band rows, bands per plane, planes per item, plane groups
@@ -116,7 +73,7 @@ __device__ __forceinline__ void fill_tile(float* tile, const T* __restrict__ src
         for (int u = 0; u < U; ++u) {
             const int v = min(v0 + u * 64 + lane, total - 1);
             const int p = fast_div(v, nvpp, inv_nvpp), e = v - p * nvpp, r = fast_div(e, wv, inv_wv), cv = e - r * wv;
-            Vec<T, VEC>::ld(src + (size_t)p * plane_stride + (size_t)(ya + r) * W + cv * VEC, val[u]);
+            PV<T, VEC>::ld(src + (size_t)p * plane_stride + (size_t)(ya + r) * W + cv * VEC, val[u]);
             dst[u] = (p * rows + (ya - y0) + r) * pitch + xo + cv * VEC;
             if constexpr (PRE) { sc[u] = ssl[p * ss_stride]; sf[u] = ssl[p * ss_stride + 1]; }
         }
@@ -131,7 +88,7 @@ __device__ __forceinline__ void fill_tile(float* tile, const T* __restrict__ src
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (v0 + u * 64 + lane < total) lds_store<VEC>(tile + dst[u], val[u]);
+            if (v0 + u * 64 + lane < total) PV<float, VEC>::st(tile + dst[u], val[u]);
     }
     // rows outside the image (wave-uniform, only at a plane's first / last band).  With one band per plane the row
     // mapping never changes and those rows keep the zeros of the initial clear: zero_rows = false.
@@ -212,11 +169,11 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_fwd_kernel(const T* __restri
                 T* o = yp + (size_t)(oy0 + strip * R) * sh.OW + ox;
                 if (strip * R + R <= th) {       // whole strip inside the band: no per-row guards
 #pragma unroll
-                    for (int r = 0; r < R; ++r) st<T>(o + r * sh.OW, acc[r]);
+                    for (int r = 0; r < R; ++r) st1<T>(o + r * sh.OW, acc[r]);
                 } else {
 #pragma unroll
                     for (int r = 0; r < R; ++r)
-                        if (strip * R + r < th) st<T>(o + r * sh.OW, acc[r]);
+                        if (strip * R + r < th) st1<T>(o + r * sh.OW, acc[r]);
                 }
             }
         }
@@ -276,7 +233,7 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_small_kernel(const T* __rest
             }
             T* o = y + ((size_t)(plane0 + p) * OWT + oy) * OWT;
 #pragma unroll
-            for (int ox = 0; ox < OWT; ++ox) st<T>(o + ox, acc[ox]);
+            for (int ox = 0; ox < OWT; ++ox) st1<T>(o + ox, acc[ox]);
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
     }
@@ -333,7 +290,7 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_bwd_data_s2_kernel(const T* 
 #pragma unroll
                             for (int s = 0; f + 2 * s < K; ++s) acc = fmaf(wk[(e + 2 * t) * K + f + 2 * s], g[t][s], acc);
                         const int iy = 2 * (a0 + ar) + e - sh.pt, ix = 2 * b + f - sh.pl;
-                        if (iy >= 0 && iy < sh.OH && ix >= 0 && ix < sh.OW) st<T>(xp + (size_t)iy * sh.OW + ix, acc);
+                        if (iy >= 0 && iy < sh.OH && ix >= 0 && ix < sh.OW) st1<T>(xp + (size_t)iy * sh.OW + ix, acc);
                     }
             }
         }
@@ -396,11 +353,7 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_bwd_weight_kernel(const T* _
                 float g[R];
                 if constexpr (GDIRECT) {
 #pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        float t1[1];
-                        Vec<T, 1>::ld(gd + (size_t)min(oy0 + strip * R + r, sh.OH - 1) * sh.OW + ox, t1);
-                        g[r] = t1[0];
-                    }
+                    for (int r = 0; r < R; ++r) g[r] = ld1<T>(gd + (size_t)min(oy0 + strip * R + r, sh.OH - 1) * sh.OW + ox);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         asm volatile("" : "+v"(g[r]));         // keep the loads unconditional and together
@@ -446,12 +399,8 @@ __global__ void dw_bwd_weight_finalize_kernel(const float* __restrict__ partial,
 
 // ---- host-side shape planning -------------------------------------------------------------------------
 int round4(int v) { return (v + 3) & ~3; }
-int pick_vec(int W, int elem_bytes, const void* a) {
-    const int maxv = 16 / elem_bytes;                           // 8 for bf16, 4 for fp32
-    for (int v = maxv; v > 1; v >>= 1)
-        if (W % v == 0 && (uintptr_t)a % (v * elem_bytes) == 0) return v;
-    return 1;
-}
+// 16 / 8 / 4 bytes (every power of two from 16 / elem_bytes elements down to 2) or one element: a vector never straddles a row
+int dw_vec(int W, int elem_bytes, const void* a) { return pick_vec(W, elem_bytes, (uintptr_t)a, {16 / elem_bytes, 4, 2}); }
 int strip_rows(int OH) { return OH >= 28 ? 4 : (OH >= 14 ? 2 : 1); }
 int planes_per_item(int OH, int OW, int nbands) {
     if (nbands > 1) return 1;
@@ -478,18 +427,10 @@ unsigned grid_for(long nitems) {
     return (unsigned)max(1L, g);
 }
 
-// run BODY with `V` = the compile-time vector width for the run-time `vec` (8 only exists for 2-byte elements)
-#define MOMA_DW_VEC_SWITCH(vec, MAXV, BODY)                                    \
-    if (MAXV >= 8 && (vec) == 8) { constexpr int V = (MAXV >= 8 ? 8 : 4); BODY; } \
-    else if ((vec) >= 4) { constexpr int V = 4; BODY; }                        \
-    else if ((vec) == 2) { constexpr int V = 2; BODY; }                        \
-    else { constexpr int V = 1; BODY; }
-
 // y (OH x OW) from x (H x W); also backward-data stride 1 with flip = true (then x = dy and y = dx)
 template <typename T, int K, int S>
 hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, int OH, int OW, int pt, int pl, bool flip,
                  const float* ss, int act, hipStream_t st) {
-    constexpr int MAXV = 16 / sizeof(T);
     if (flip && ss) return hipErrorInvalidValue;
     DwShape sh{};
     sh.NC = NC; sh.C = C; sh.H = H; sh.W = W; sh.OH = OH; sh.OW = OW; sh.pt = pt; sh.pl = pl;
@@ -508,13 +449,13 @@ hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, 
         if (lds0 <= (size_t)LDS_BUDGET) {
             if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
             const dim3 grid(grid_for(sh.ngroups)), block(DW_WAVES * 64);
-            const int vec = 1;       // (odd pitch: element stores into the tile)
+            const int vec = 1;       // (odd pitch: element stores into the tile; the wider instantiations below are never launched)
 #define MOMA_DW_SMALL(OWT, FL, PR) \
     hipLaunchKernelGGL((dw_small_kernel<T, K, S, OWT, FL, V, PR>), grid, block, lds, st, x, w, y, sh, ss, act)
-            MOMA_DW_VEC_SWITCH(vec, MAXV, {
+            with_vec<MAXVEC<T>, 8, 4, 2, 1>(vec, [&](auto V) {
                 if (OW == 7) { if (flip) MOMA_DW_SMALL(7, true, false); else if (ss) MOMA_DW_SMALL(7, false, true); else MOMA_DW_SMALL(7, false, false); }
                 else { if (flip) MOMA_DW_SMALL(14, true, false); else if (ss) MOMA_DW_SMALL(14, false, true); else MOMA_DW_SMALL(14, false, false); }
-            })
+            });
 #undef MOMA_DW_SMALL
             return hipGetLastError();
         }
@@ -529,14 +470,14 @@ hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, 
                        sizeof(float);
     if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
     const dim3 grid(grid_for((long)sh.ngroups * sh.nbands)), block(DW_WAVES * 64);
-    const int vec = pick_vec(W, sizeof(T), x);
+    const int vec = dw_vec(W, sizeof(T), x);
 #define MOMA_DW_GO(RR, FL, PR) \
     hipLaunchKernelGGL((dw_fwd_kernel<T, K, S, RR, FL, V, PR>), grid, block, lds, st, x, w, y, sh, ss, act)
-    MOMA_DW_VEC_SWITCH(vec, MAXV, {
+    with_vec<MAXVEC<T>, 8, 4, 2, 1>(vec, [&](auto V) {
         if (flip) { if (R == 4) MOMA_DW_GO(4, true, false); else if (R == 2) MOMA_DW_GO(2, true, false); else MOMA_DW_GO(1, true, false); }
         else if (ss) { if (R == 4) MOMA_DW_GO(4, false, true); else if (R == 2) MOMA_DW_GO(2, false, true); else MOMA_DW_GO(1, false, true); }
         else { if (R == 4) MOMA_DW_GO(4, false, false); else if (R == 2) MOMA_DW_GO(2, false, false); else MOMA_DW_GO(1, false, false); }
-    })
+    });
 #undef MOMA_DW_GO
     return hipGetLastError();
 }
@@ -545,7 +486,6 @@ hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, 
 template <typename T, int K>
 hipError_t bwd_data_s2_t(const T* dy, const float* w, T* dx, int NC, int C, int H, int W, int OH, int OW, int pt, int pl,
                          hipStream_t st) {
-    constexpr int MAXV = 16 / sizeof(T);
     constexpr int HT = (K - 1) / 2;
     DwShape sh{};
     sh.NC = NC; sh.C = C; sh.H = OH; sh.W = OW; sh.OH = H; sh.OW = W; sh.pt = pt; sh.pl = pl;       // source = dy, result = dx
@@ -562,15 +502,16 @@ hipError_t bwd_data_s2_t(const T* dy, const float* w, T* dx, int NC, int C, int 
     const size_t lds = (size_t)DW_WAVES * (sh.PB * sh.IR * sh.pitch + round4(sh.PB * K * K)) * sizeof(float);
     if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
     const dim3 grid(grid_for((long)sh.ngroups * sh.nbands)), block(DW_WAVES * 64);
-    const int vec = pick_vec(OW, sizeof(T), dy);
-    MOMA_DW_VEC_SWITCH(vec, MAXV, { hipLaunchKernelGGL((dw_bwd_data_s2_kernel<T, K, V>), grid, block, lds, st, dy, w, dx, sh); })
+    const int vec = dw_vec(OW, sizeof(T), dy);
+    with_vec<MAXVEC<T>, 8, 4, 2, 1>(vec, [&](auto V) {
+        hipLaunchKernelGGL((dw_bwd_data_s2_kernel<T, K, V>), grid, block, lds, st, dy, w, dx, sh);
+    });
     return hipGetLastError();
 }
 
 template <typename T, int K, int S>
 hipError_t bwd_weight_t(const T* x, const T* dy, float* dw, float* ws, size_t ws_floats, int N, int C, int H, int W, int OH,
                         int OW, int pt, int pl, const float* ss, int act, hipStream_t st) {
-    constexpr int MAXV = 16 / sizeof(T);
     DwShape sh{};
     sh.NC = N * C; sh.C = C; sh.H = H; sh.W = W; sh.OH = OH; sh.OW = OW; sh.pt = pt; sh.pl = pl;
     sh.pitch = round4(XO + max(W, (OW - 1) * S + K - pl) + 1);
@@ -590,16 +531,16 @@ hipError_t bwd_weight_t(const T* x, const T* dy, float* dw, float* ws, size_t ws
     while (nsplit_wg > 1 && (size_t)C * nsplit_wg * DW_WAVES * K * K > ws_floats) --nsplit_wg;
     if ((size_t)C * nsplit_wg * DW_WAVES * K * K > ws_floats) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nsplit_wg, C), block(DW_WAVES * 64);
-    const int vec = pick_vec(W, sizeof(T), x), gvec = pick_vec(OW, sizeof(T), dy);
+    const int vec = dw_vec(W, sizeof(T), x), gvec = dw_vec(OW, sizeof(T), dy);
     // (the dy tile takes the x tile's vector width when that divides OW too, else scalar: keeps the instantiations down)
 #define MOMA_DW_GO1(RR, GV, GD, PR) \
     hipLaunchKernelGGL((dw_bwd_weight_kernel<T, K, S, RR, V, GV, GD, PR>), grid, block, lds, st, x, dy, ws, sh, N, ss, act)
 #define MOMA_DW_GO(RR, GV, GD) { if (ss) MOMA_DW_GO1(RR, GV, GD, true); else MOMA_DW_GO1(RR, GV, GD, false); }
-    MOMA_DW_VEC_SWITCH(vec, MAXV, {
+    with_vec<MAXVEC<T>, 8, 4, 2, 1>(vec, [&](auto V) {
         if (gdirect) { if (R == 4) MOMA_DW_GO(4, 1, true) else if (R == 2) MOMA_DW_GO(2, 1, true) else MOMA_DW_GO(1, 1, true) }
         else if (gvec >= V) { if (R == 4) MOMA_DW_GO(4, V, false) else if (R == 2) MOMA_DW_GO(2, V, false) else MOMA_DW_GO(1, V, false) }
         else { if (R == 4) MOMA_DW_GO(4, 1, false) else if (R == 2) MOMA_DW_GO(2, 1, false) else MOMA_DW_GO(1, 1, false) }
-    })
+    });
 #undef MOMA_DW_GO1
 #undef MOMA_DW_GO
     const int total = C * K * K;
@@ -621,50 +562,42 @@ size_t dwconv_workspace_floats(int C, int K) { return (size_t)C * 64 * DW_WAVES 
 
 hipError_t launch_dw_fwd(const void* x, const float* w, void* y, int N, int C, int H, int W, int OH, int OW, int K, int S,
                          int pt, int pl, int dtype, const float* scale_shift, int act, hipStream_t st) {
-    if (dtype == MOMA_DT_BF16) {
-#define CALL(KK, SS) fwd_t<bf16_raw, KK, SS>((const bf16_raw*)x, w, (bf16_raw*)y, N * C, C, H, W, OH, OW, pt, pl, false, scale_shift, act, st)
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+#define CALL(KK, SS) fwd_t<T, KK, SS>((const T*)x, w, (T*)y, N * C, C, H, W, OH, OW, pt, pl, false, scale_shift, act, st)
         MOMA_DW_DISPATCH(CALL)
 #undef CALL
-    }
-#define CALL(KK, SS) fwd_t<float, KK, SS>((const float*)x, w, (float*)y, N * C, C, H, W, OH, OW, pt, pl, false, scale_shift, act, st)
-    MOMA_DW_DISPATCH(CALL)
-#undef CALL
+    });
 }
 
 hipError_t launch_dw_bwd_data(const void* dy, const float* w, void* dx, int N, int C, int H, int W, int OH, int OW, int K,
                               int S, int pt, int pl, int dtype, hipStream_t st) {
-    if (S == 1) {
-        // correlation of dy with the flipped filter, padding K-1-pt / K-1-pl; result plane = the input plane
-        if (dtype == MOMA_DT_BF16) {
-            if (K == 3) return fwd_t<bf16_raw, 3, 1>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, OH, OW, H, W, 2 - pt, 2 - pl, true, nullptr, 0, st);
-            if (K == 5) return fwd_t<bf16_raw, 5, 1>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, OH, OW, H, W, 4 - pt, 4 - pl, true, nullptr, 0, st);
-        } else {
-            if (K == 3) return fwd_t<float, 3, 1>((const float*)dy, w, (float*)dx, N * C, C, OH, OW, H, W, 2 - pt, 2 - pl, true, nullptr, 0, st);
-            if (K == 5) return fwd_t<float, 5, 1>((const float*)dy, w, (float*)dx, N * C, C, OH, OW, H, W, 4 - pt, 4 - pl, true, nullptr, 0, st);
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const T* g = (const T*)dy;
+        T* o = (T*)dx;
+        if (S == 1) {
+            // correlation of dy with the flipped filter, padding K-1-pt / K-1-pl; result plane = the input plane
+            if (K == 3) return fwd_t<T, 3, 1>(g, w, o, N * C, C, OH, OW, H, W, 2 - pt, 2 - pl, true, nullptr, 0, st);
+            if (K == 5) return fwd_t<T, 5, 1>(g, w, o, N * C, C, OH, OW, H, W, 4 - pt, 4 - pl, true, nullptr, 0, st);
+            return hipErrorInvalidValue;
         }
+        if (K == 3) return bwd_data_s2_t<T, 3>(g, w, o, N * C, C, H, W, OH, OW, pt, pl, st);
+        if (K == 5) return bwd_data_s2_t<T, 5>(g, w, o, N * C, C, H, W, OH, OW, pt, pl, st);
         return hipErrorInvalidValue;
-    }
-    if (dtype == MOMA_DT_BF16) {
-        if (K == 3) return bwd_data_s2_t<bf16_raw, 3>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, H, W, OH, OW, pt, pl, st);
-        if (K == 5) return bwd_data_s2_t<bf16_raw, 5>((const bf16_raw*)dy, w, (bf16_raw*)dx, N * C, C, H, W, OH, OW, pt, pl, st);
-    } else {
-        if (K == 3) return bwd_data_s2_t<float, 3>((const float*)dy, w, (float*)dx, N * C, C, H, W, OH, OW, pt, pl, st);
-        if (K == 5) return bwd_data_s2_t<float, 5>((const float*)dy, w, (float*)dx, N * C, C, H, W, OH, OW, pt, pl, st);
-    }
-    return hipErrorInvalidValue;
+    });
 }
 
 hipError_t launch_dw_bwd_weight(const void* x, const void* dy, float* dw, float* ws, size_t ws_floats, int N, int C, int H,
                                 int W, int OH, int OW, int K, int S, int pt, int pl, int dtype, const float* scale_shift, int act,
                                 hipStream_t st) {
-    if (dtype == MOMA_DT_BF16) {
-#define CALL(KK, SS) bwd_weight_t<bf16_raw, KK, SS>((const bf16_raw*)x, (const bf16_raw*)dy, dw, ws, ws_floats, N, C, H, W, OH, OW, pt, pl, scale_shift, act, st)
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+#define CALL(KK, SS) \
+    bwd_weight_t<T, KK, SS>((const T*)x, (const T*)dy, dw, ws, ws_floats, N, C, H, W, OH, OW, pt, pl, scale_shift, act, st)
         MOMA_DW_DISPATCH(CALL)
 #undef CALL
-    }
-#define CALL(KK, SS) bwd_weight_t<float, KK, SS>((const float*)x, (const float*)dy, dw, ws, ws_floats, N, C, H, W, OH, OW, pt, pl, scale_shift, act, st)
-    MOMA_DW_DISPATCH(CALL)
-#undef CALL
+    });
 }
 
 }  // namespace moma

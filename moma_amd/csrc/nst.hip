@@ -52,27 +52,15 @@ struct NstShape {
     int vec_s, vec_t;                       // 16-byte loads are possible on that side
 };
 
-template <typename T> struct NstVec;
-template <> struct NstVec<float> { static constexpr int V = 4; };
-template <> struct NstVec<bf16_raw> { static constexpr int V = 8; };
-
 // row of accumulator register `reg` in a 32 x 32 MFMA result (the column is lane & 31)
 __device__ __forceinline__ int nst_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-// double -> float as a rounding of its own: written as a plain cast in front of a bf16 store the compiler merges the two roundings
-// into one double -> bf16 conversion, and a value that is a tie in fp32 then lands on the other side of what the fp32 output rounds to
-__device__ __forceinline__ float nst_f32(double d) {
-    float f = (float)d;
-    asm("" : "+v"(f));
-    return f;
-}
 
 // channels [c0, c0 + nc) x pixels [p0, p0 + 2^lg) of one image -> lds[(c - c0) * ld + (p - p0)] as fp32, zero where p >= P.
 // vec: c0 and nc are multiples of the vector width (channels_last), p0 is (NCHW), and the side's base is 16-byte aligned
 template <typename T>
 __device__ __forceinline__ void nst_stage(const T* __restrict__ fb, int C, int P, int nhwc, int vec, int c0, int nc, int p0, int lg,
                                           float* __restrict__ lds, int ld) {
-    constexpr int V = NstVec<T>::V, LGV = V == 8 ? 3 : 2;
+    constexpr int V = MAXVEC<T>, LGV = V == 8 ? 3 : 2;
     const int tid = threadIdx.x, TP = 1 << lg;                     // tile width in pixels: 16 .. 128
     if (!nhwc) {
         if (vec) {
@@ -345,14 +333,14 @@ __global__ __launch_bounds__(NST_THREADS) void nst_bwd_kernel(const TS* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int i = i0 + nst_row(r, h);
-                if (i < Cs) st1<TS>(dFb + (size_t)i * P + p, nst_f32(tot[s][r]));
+                if (i < Cs) st1<TS>(dFb + (size_t)i * P + p, round_f32(tot[s][r]));
             }
         } else if (vec_out) {                                     // Cs % 4 == 0: registers 4g .. 4g + 3 are four neighbouring channels
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int i = i0 + 8 * g + 4 * h;
                 if (i < Cs) {
-                    const float v[4] = {nst_f32(tot[s][4 * g]), nst_f32(tot[s][4 * g + 1]), nst_f32(tot[s][4 * g + 2]), nst_f32(tot[s][4 * g + 3])};
+                    const float v[4] = {round_f32(tot[s][4 * g]), round_f32(tot[s][4 * g + 1]), round_f32(tot[s][4 * g + 2]), round_f32(tot[s][4 * g + 3])};
                     PV<TS, 4>::st(dFb + (size_t)p * Cs + i, v);
                 }
             }
@@ -360,24 +348,24 @@ __global__ __launch_bounds__(NST_THREADS) void nst_bwd_kernel(const TS* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int i = i0 + nst_row(r, h);
-                if (i < Cs) st1<TS>(dFb + (size_t)p * Cs + i, nst_f32(tot[s][r]));
+                if (i < Cs) st1<TS>(dFb + (size_t)p * Cs + i, round_f32(tot[s][r]));
             }
         }
     }
 }
 
-// 16-byte accesses along the contiguous extent (P in NCHW, C in channels_last) of a side
-int nst_vec(const void* p, int extent, int dtype) {
-    const int V = dtype == MOMA_DT_BF16 ? 8 : 4;
-    return extent % V == 0 && (uintptr_t)p % 16 == 0;
+// 16-byte accesses along the contiguous extent (P in NCHW, C in channels_last) of a side, or element accesses
+int nst_wide(const void* p, int extent, int dtype) {
+    const int eb = dtype == MOMA_DT_BF16 ? 2 : 4;
+    return pick_vec(extent, eb, (uintptr_t)p, {16 / eb}) > 1;
 }
 NstShape nst_shape(const void* fs, const void* ft, int B, int Cs, int Ct, int P, int dt_s, int lay_s, int dt_t, int lay_t) {
     NstShape q;
     q.B = B; q.Cs = Cs; q.Ct = Ct; q.P = P;
     q.nhwc_s = lay_s == MOMA_LAYOUT_NHWC;
     q.nhwc_t = lay_t == MOMA_LAYOUT_NHWC;
-    q.vec_s = nst_vec(fs, q.nhwc_s ? Cs : P, dt_s);
-    q.vec_t = nst_vec(ft, q.nhwc_t ? Ct : P, dt_t);
+    q.vec_s = nst_wide(fs, q.nhwc_s ? Cs : P, dt_s);
+    q.vec_t = nst_wide(ft, q.nhwc_t ? Ct : P, dt_t);
     return q;
 }
 
@@ -403,19 +391,18 @@ void nst_bwd_t(const void* fs, const void* ft, const float* G, const float* norm
     hipLaunchKernelGGL((nst_bwd_kernel<TS, TT>), dim3((unsigned)((long long)q.B * ptiles)), dim3(NST_THREADS), 0, st, (const TS*)fs,
                        (const TT*)ft, G, norms, rows, g_loss, (TS*)dF, q, vec_out, ptiles, alpha, beta);
 }
-#define NST_DISPATCH(FN, ...)                                                                        \
-    do {                                                                                             \
-        if (dt_s == MOMA_DT_BF16 && dt_t == MOMA_DT_BF16) FN<bf16_raw, bf16_raw>(__VA_ARGS__);       \
-        else if (dt_s == MOMA_DT_BF16) FN<bf16_raw, float>(__VA_ARGS__);                             \
-        else if (dt_t == MOMA_DT_BF16) FN<float, bf16_raw>(__VA_ARGS__);                             \
-        else FN<float, float>(__VA_ARGS__);                                                          \
-    } while (0)
+// f(TypeTag<TS>, TypeTag<TT>) for the storage types of the two sides
+template <typename F> void nst_dispatch(int dt_s, int dt_t, F&& f) {
+    with_dtype(dt_s, [&](auto ts) { return with_dtype(dt_t, [&](auto tt) { f(ts, tt); return 0; }); });
+}
 
 hipError_t launch_nst_gram(const void* fs, const void* ft, int B, int Cs, int Ct, int P, int dt_s, int lay_s, int dt_t, int lay_t,
                            float* G, float* norms, float* rows, float* partials, float* terms, float* loss, hipStream_t st) {
     const NstShape q = nst_shape(fs, ft, B, Cs, Ct, P, dt_s, lay_s, dt_t, lay_t);
     const int nrb = (int)nst_row_blocks(Cs);
-    NST_DISPATCH(nst_gram_t, fs, ft, G, norms, rows, partials, q, nrb, st);
+    nst_dispatch(dt_s, dt_t, [&](auto ts, auto tt) {
+        nst_gram_t<typename decltype(ts)::type, typename decltype(tt)::type>(fs, ft, G, norms, rows, partials, q, nrb, st);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(nst_loss_kernel, dim3(1), dim3(NST_THREADS), 0, st, (const float*)partials, (long long)B * nrb, terms, loss,
@@ -429,7 +416,10 @@ hipError_t launch_nst_bwd(const void* fs, const void* ft, const float* G, const 
     const int ptiles = (int)nst_pixel_tiles(P);
     const int vec_out = q.nhwc_s && Cs % 4 == 0 && (uintptr_t)dF % 16 == 0;
     const double alpha = 4.0 / ((double)B * Cs * Cs), beta = 4.0 / ((double)B * Cs * Ct);
-    NST_DISPATCH(nst_bwd_t, fs, ft, G, norms, rows, g_loss, dF, q, vec_out, ptiles, alpha, beta, st);
+    nst_dispatch(dt_s, dt_t, [&](auto ts, auto tt) {
+        nst_bwd_t<typename decltype(ts)::type, typename decltype(tt)::type>(fs, ft, G, norms, rows, g_loss, dF, q, vec_out, ptiles, alpha,
+                                                                            beta, st);
+    });
     return hipGetLastError();
 }
 

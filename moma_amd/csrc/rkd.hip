@@ -48,17 +48,6 @@ constexpr int RKD_LDM = RKD_BJ + 1;          // row stride of the M slab (double
 constexpr int RKD_LDX = RKD_BC + 16;         // row stride of the X slab: two consecutive k rows in disjoint halves of the banks
 constexpr double RKD_EPS = 1e-12;
 
-template <typename T> struct RkdVec;
-template <> struct RkdVec<float> { static constexpr int V = 4; };
-template <> struct RkdVec<bf16_raw> { static constexpr int V = 8; };
-
-// double -> float as a rounding of its own (see nst_f32): in front of a bf16 store the compiler would merge the two roundings
-__device__ __forceinline__ float rkd_f32(double d) {
-    float f = (float)d;
-    asm("" : "+v"(f));
-    return f;
-}
-
 __device__ __forceinline__ double rkd_sl1(double z) {
     const double a = fabs(z);
     return a < 1.0 ? 0.5 * z * z : a - 0.5;
@@ -67,8 +56,7 @@ __device__ __forceinline__ double rkd_clip(double z) { return fmin(fmax(z, -1.0)
 
 // sum over the workgroup in a fixed order (butterfly inside a wave, then waves 0, 1, 2, 3), the result in every thread
 __device__ __forceinline__ double rkd_block_sum(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     __syncthreads();                                              // (sh may still be read from the previous call)
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -85,7 +73,7 @@ __device__ __forceinline__ double rkd_array_sum(const double* __restrict__ a, in
 // vec: D is a multiple of the vector width and the base is 16-byte aligned (k0 is a multiple of 128)
 template <typename T>
 __device__ __forceinline__ void rkd_stage(const T* __restrict__ f, int B, int D, int vec, int r0, long long k0, double* __restrict__ lds) {
-    constexpr int V = RkdVec<T>::V, VPR = RKD_KD / V;             // vectors per row of the slab
+    constexpr int V = MAXVEC<T>, VPR = RKD_KD / V;             // vectors per row of the slab
     const int tid = threadIdx.x;
     if (vec) {
         for (int idx = tid; idx < RKD_T * VPR; idx += RKD_THREADS) {
@@ -330,7 +318,7 @@ __global__ __launch_bounds__(RKD_THREADS) void rkd_bwd_kernel(const T* __restric
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = i0 + 16 * rt + l4 + 4 * r;              // C/D layout of the f64 MFMA: row = (lane >> 4) + 4 reg
-            if (i < B) st1<T>(dX + (size_t)i * D + c, rkd_f32(g * acc[rt][r]));
+            if (i < B) st1<T>(dX + (size_t)i * D + c, round_f32(g * acc[rt][r]));
         }
 }
 
@@ -346,13 +334,12 @@ size_t rkd_workspace_bytes(int B) {
 
 hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st) {
     const int nt = rkd_tiles(B);
-    const int V = dtype == MOMA_DT_BF16 ? 8 : 4;
-    const int vec = D % V == 0 && (uintptr_t)f % 16 == 0;
-    if (dtype == MOMA_DT_BF16)
-        hipLaunchKernelGGL(rkd_dist_kernel<bf16_raw>, dim3(nt, nt), dim3(RKD_THREADS), 0, st, (const bf16_raw*)f, S, B, (int)D, vec);
-    else
-        hipLaunchKernelGGL(rkd_dist_kernel<float>, dim3(nt, nt), dim3(RKD_THREADS), 0, st, (const float*)f, S, B, (int)D, vec);
-    return hipGetLastError();
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const int vec = pick_vec(D, sizeof(T), (uintptr_t)f, {MAXVEC<T>}) > 1;      // 16 bytes or nothing
+        hipLaunchKernelGGL(rkd_dist_kernel<T>, dim3(nt, nt), dim3(RKD_THREADS), 0, st, (const T*)f, S, B, (int)D, vec);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_rkd_terms(const double* S_s, const double* S_t, int B, double w_d, double w_a, void* ws, double* Q, float* terms,
@@ -377,11 +364,11 @@ hipError_t launch_rkd_terms(const double* S_s, const double* S_t, int B, double 
 hipError_t launch_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF, int B, long long D, int dtype,
                           hipStream_t st) {
     const dim3 grid((unsigned)((D + RKD_BC - 1) / RKD_BC), (unsigned)((B + RKD_BR - 1) / RKD_BR));
-    if (dtype == MOMA_DT_BF16)
-        hipLaunchKernelGGL(rkd_bwd_kernel<bf16_raw>, grid, dim3(RKD_THREADS), 0, st, (const bf16_raw*)f_s, Q, g_loss, (bf16_raw*)dF, B, (int)D);
-    else
-        hipLaunchKernelGGL(rkd_bwd_kernel<float>, grid, dim3(RKD_THREADS), 0, st, (const float*)f_s, Q, g_loss, (float*)dF, B, (int)D);
-    return hipGetLastError();
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(rkd_bwd_kernel<T>, grid, dim3(RKD_THREADS), 0, st, (const T*)f_s, Q, g_loss, (T*)dF, B, (int)D);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace moma

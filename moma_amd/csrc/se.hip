@@ -79,58 +79,46 @@ __global__ __launch_bounds__(SE_WAVES * 64) void se_gate_bwd_kernel(const T* __r
     }
 }
 
-int se_vec(int HW, int elem_bytes, uintptr_t bits) {
-    const int maxv = 16 / elem_bytes;
-    for (int v = maxv; v > 1; v >>= 1)
-        if (v != 2 && HW % v == 0 && bits % (v * elem_bytes) == 0) return v;
-    return 1;
-}
 unsigned se_grid(int NC) {
     long g = ((long)NC + SE_WAVES - 1) / SE_WAVES;
     if (g > 256 * 32) g = 256 * 32;
     return (unsigned)(g < 1 ? 1 : g);
 }
+// 16 bytes / 4 elements / 1 (never 2) along the plane; `bits` = the OR of the addresses accessed at that width
+template <typename T, typename F> void se_launch(int NC, int HW, uintptr_t bits, F&& f) {
+    const int vec = pick_vec(HW, sizeof(T), bits, {MAXVEC<T>, 4});
+    with_vec<MAXVEC<T>, 8, 4, 1>(vec, [&](auto V) { f(V, dim3(se_grid(NC)), dim3(SE_WAVES * 64)); });
+}
 }  // namespace
 
-#define MOMA_SE_LAUNCH(KERNEL, T, MAXV, ...)                                                                       \
-    do {                                                                                                           \
-        if (MAXV == 8 && vec == 8) hipLaunchKernelGGL((KERNEL<T, MAXV>), dim3(se_grid(NC)), dim3(SE_WAVES * 64), 0, st, __VA_ARGS__); \
-        else if (vec >= 4) hipLaunchKernelGGL((KERNEL<T, 4>), dim3(se_grid(NC)), dim3(SE_WAVES * 64), 0, st, __VA_ARGS__);            \
-        else hipLaunchKernelGGL((KERNEL<T, 1>), dim3(se_grid(NC)), dim3(SE_WAVES * 64), 0, st, __VA_ARGS__);                          \
-    } while (0)
-
 hipError_t launch_plane_mean(const void* x, void* out, int NC, int HW, int dtype, hipStream_t st) {
-    if (dtype == MOMA_DT_BF16) {
-        const int vec = se_vec(HW, 2, (uintptr_t)x);
-        MOMA_SE_LAUNCH(plane_mean_kernel, bf16_raw, 8, (const bf16_raw*)x, (bf16_raw*)out, NC, HW);
-    } else {
-        const int vec = se_vec(HW, 4, (uintptr_t)x);
-        MOMA_SE_LAUNCH(plane_mean_kernel, float, 4, (const float*)x, (float*)out, NC, HW);
-    }
-    return hipGetLastError();
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        se_launch<T>(NC, HW, (uintptr_t)x, [&](auto V, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((plane_mean_kernel<T, V>), grid, block, 0, st, (const T*)x, (T*)out, NC, HW);
+        });
+        return hipGetLastError();
+    });
 }
 hipError_t launch_se_gate_fwd(const void* x, const void* s, void* out, int NC, int HW, int dtype, hipStream_t st) {
-    if (dtype == MOMA_DT_BF16) {
-        const int vec = se_vec(HW, 2, (uintptr_t)x | (uintptr_t)out);
-        MOMA_SE_LAUNCH(se_gate_fwd_kernel, bf16_raw, 8, (const bf16_raw*)x, (const bf16_raw*)s, (bf16_raw*)out, NC, HW);
-    } else {
-        const int vec = se_vec(HW, 4, (uintptr_t)x | (uintptr_t)out);
-        MOMA_SE_LAUNCH(se_gate_fwd_kernel, float, 4, (const float*)x, (const float*)s, (float*)out, NC, HW);
-    }
-    return hipGetLastError();
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        se_launch<T>(NC, HW, (uintptr_t)x | (uintptr_t)out, [&](auto V, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((se_gate_fwd_kernel<T, V>), grid, block, 0, st, (const T*)x, (const T*)s, (T*)out, NC, HW);
+        });
+        return hipGetLastError();
+    });
 }
 hipError_t launch_se_gate_bwd(const void* x, const void* s, const void* dout, void* dx, void* ds, int NC, int HW, int dtype,
                               hipStream_t st) {
-    if (dtype == MOMA_DT_BF16) {
-        const int vec = se_vec(HW, 2, (uintptr_t)x | (uintptr_t)dout | (uintptr_t)dx);
-        MOMA_SE_LAUNCH(se_gate_bwd_kernel, bf16_raw, 8, (const bf16_raw*)x, (const bf16_raw*)s, (const bf16_raw*)dout,
-                       (bf16_raw*)dx, (bf16_raw*)ds, NC, HW);
-    } else {
-        const int vec = se_vec(HW, 4, (uintptr_t)x | (uintptr_t)dout | (uintptr_t)dx);
-        MOMA_SE_LAUNCH(se_gate_bwd_kernel, float, 4, (const float*)x, (const float*)s, (const float*)dout, (float*)dx,
-                       (float*)ds, NC, HW);
-    }
-    return hipGetLastError();
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        se_launch<T>(NC, HW, (uintptr_t)x | (uintptr_t)dout | (uintptr_t)dx, [&](auto V, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((se_gate_bwd_kernel<T, V>), grid, block, 0, st, (const T*)x, (const T*)s, (const T*)dout, (T*)dx,
+                               (T*)ds, NC, HW);
+        });
+        return hipGetLastError();
+    });
 }
 
 }  // namespace moma
