@@ -334,6 +334,41 @@ int moma_rkd_terms(const double* S_s, const double* S_t, int B, float w_d, float
 int moma_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF_s, int B, int D, int dtype, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SP  Similarity-Preserving distillation (`--distill similarity`) on one pair of feature maps -- replaces Similarity.similarity_loss
+ *     (distiller_zoo/SP.py: view(bsz, -1) -> mm with its transpose -> F.normalize(dim=1) per side -> mean squared difference) and
+ *     its autograd backward to f_s.  X = f_s as [B, Ks], Y = f_t as [B, Kt] (Ks and Kt may differ), all indices over the batch:
+ *         G = X X^T    n_i = max(|G_i|_2, 1e-12)    H = G / n (row-wise)    (per side)
+ *         loss = (1/B^2) sum_ij (H^t_ij - H^s_ij)^2
+ *         E = -(2/B^2) (H^t - H^s)    Q_i = (E_i - (E_i . H^s_i) H^s_i) / n^s_i   (the projection only where |G^s_i| >= 1e-12: the clamp)
+ *         M = Q + Q^T    dF_s = g_loss M X
+ *     G is invariant under a permutation of the K columns applied to every row alike, so f is read IN STORAGE ORDER as [B, K] with
+ *     row stride K and dF_s is written in that order: an NCHW-contiguous map and a channels_last map are both passed as they lie in
+ *     memory, no layout flag exists.  Required: sample 0 is dense and every sample has the same strides.
+ *     f, f_s, dF_s: MOMA_DT_F32 or MOMA_DT_BF16, aligned to their element size (16-byte loads where the base address and K allow,
+ *     element loads otherwise).  The products run on the f32-input MFMA (fp32 storage) or the bf16-input MFMA (bf16 storage: the
+ *     products of two bf16 are exact in its fp32 accumulator); an fp32 accumulation chain is one staged slab long -- 64 columns for
+ *     fp32 storage, 128 for bf16 -- and is then added to a double total.  A split's double total is rounded ONCE to fp32 when the
+ *     partial is written (half an fp32 ulp of the partial at most); moma_sp_terms adds the partials of a side in double, in the order
+ *     of the splits.  G, H, rows, M are double, 8-byte aligned; loss and g_loss fp32.  1 <= B <= MOMA_SP_MAX_B (else
+ *     MOMA_E_UNSUPPORTED, nothing is launched), any K >= 1.  No atomics: bitwise reproducible.
+ *
+ * workspace      of ONE side: moma_sp_workspace_bytes(B, K) = splits(B, K) B^2 4 bytes, splits = min(ceil(K / 128), ceil(512 / pairs)),
+ *                pairs = nt (nt + 1) / 2, nt = ceil(B / 64): the split-K partial Gram matrices, written by moma_sp_gram and read by
+ *                moma_sp_terms.  4-byte aligned.
+ * moma_sp_gram   one side: f [B, K] -> its workspace.  Call it once for f_s and once for f_t, each with a workspace of its own.
+ * moma_sp_terms  both workspaces (with the K each was written for) -> G [2, B, B] (student, teacher), H [2, B, B], rows [4, B]
+ *                (n^s, n^t -- not clamped --, E_i . H^s_i, the row's sum of (H^t - H^s)^2), M [B, B], loss [1].
+ * moma_sp_bwd    f_s, M -> dF_s [B, K] in f_s's dtype and storage order; g_loss is a DEVICE scalar (the upstream gradient of the loss,
+ *                e.g. a GradScaler factor): nothing is read back to the host.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_SP_MAX_B = 1024 };
+size_t moma_sp_workspace_bytes(int B, long long K);
+int moma_sp_gram(const void* f, int B, long long K, int dtype, void* workspace, size_t workspace_bytes, moma_stream_t stream);
+int moma_sp_terms(const void* workspace_s, size_t workspace_s_bytes, long long Ks, const void* workspace_t, size_t workspace_t_bytes,
+                  long long Kt, int B, double* G, double* H, double* rows, double* M, float* loss, moma_stream_t stream);
+int moma_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, long long K, int dtype, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1  batch-token multi-head attention -- replaces Attention.forward
  *     (MoMA/criterion_moco_att.py:153-167) and its autograd backward.
  *     x [N,d] -> qkv = x Wqkv^T + bqkv -> per head softmax(q k^T * hd^-1/2) v -> y = a Wproj^T + bproj.

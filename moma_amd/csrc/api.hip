@@ -811,4 +811,50 @@ int moma_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF
     return hip_rc(launch_rkd_bwd(f_s, Q, g_loss, dF_s, B, D, dtype, (hipStream_t)stream));
 }
 
+// ---- Similarity-Preserving distillation ------------------------------------------------------------------------------------------
+static int sp_check(int B, long long K, int dtype) {
+    if (B <= 0 || K <= 0) return MOMA_E_SHAPE;
+    if (bad_dt(dtype)) return MOMA_E_DTYPE;
+    if (B > MOMA_SP_MAX_B) return MOMA_E_UNSUPPORTED;
+    if ((K + 63) / 64 > INT32_MAX) return MOMA_E_UNSUPPORTED;                    // (sp_bwd's grid)
+    return MOMA_OK;
+}
+
+size_t moma_sp_workspace_bytes(int B, long long K) {
+    if (sp_check(B, K, MOMA_DT_F32) != MOMA_OK) return 0;
+    return sp_workspace_bytes(B, K);
+}
+
+int moma_sp_gram(const void* f, int B, long long K, int dtype, void* workspace, size_t workspace_bytes, moma_stream_t stream) {
+    if (!f || !workspace) return MOMA_E_NULL;
+    const int rc = sp_check(B, K, dtype);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < sp_workspace_bytes(B, K)) return MOMA_E_WORKSPACE;
+    if (misaligned(f, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(workspace, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_sp_gram(f, B, K, dtype, (float*)workspace, (hipStream_t)stream));
+}
+
+int moma_sp_terms(const void* workspace_s, size_t workspace_s_bytes, long long Ks, const void* workspace_t, size_t workspace_t_bytes,
+                  long long Kt, int B, double* G, double* H, double* rows, double* M, float* loss, moma_stream_t stream) {
+    if (!workspace_s || !workspace_t || !G || !H || !rows || !M || !loss) return MOMA_E_NULL;
+    int rc = sp_check(B, Ks, MOMA_DT_F32);
+    if (rc == MOMA_OK) rc = sp_check(B, Kt, MOMA_DT_F32);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_s_bytes < sp_workspace_bytes(B, Ks) || workspace_t_bytes < sp_workspace_bytes(B, Kt)) return MOMA_E_WORKSPACE;
+    if (misaligned(workspace_s, 4) || misaligned(workspace_t, 4) || misaligned(G, 8) || misaligned(H, 8) || misaligned(rows, 8) ||
+        misaligned(M, 8) || misaligned(loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_sp_terms((const float*)workspace_s, (int)sp_splits(B, Ks), (const float*)workspace_t, (int)sp_splits(B, Kt), B, G,
+                                  H, rows, M, loss, (hipStream_t)stream));
+}
+
+int moma_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, long long K, int dtype, moma_stream_t stream) {
+    if (!f_s || !M || !g_loss || !dF_s) return MOMA_E_NULL;
+    const int rc = sp_check(B, K, dtype);
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(M, 8) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_sp_bwd(f_s, M, g_loss, dF_s, B, K, dtype, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -186,8 +186,8 @@ static_assert(pick_vec(56 * 56, 4, 0x20, {8, 4}) == 8 && pick_vec(56 * 56, 4, 0x
 static_assert(pick_vec(6, 2, 0, {8, 4}) == 1 && pick_vec(8, 4, 0, {4, 4}) == 4, "se / at");
 // dwconv.hip {16 / eb, 4, 2}: every power of two down to 2
 static_assert(pick_vec(6, 2, 0, {8, 4, 2}) == 2 && pick_vec(112, 2, 4, {8, 4, 2}) == 2, "dw");
-// nst.hip, rkd.hip {16 / eb}: 16 bytes or nothing
-static_assert(pick_vec(12, 2, 0, {8}) == 1 && pick_vec(16, 2, 0, {8}) == 8 && pick_vec(16, 2, 8, {8}) == 1, "nst / rkd");
+// nst.hip, rkd.hip, sp.hip {16 / eb}: 16 bytes or nothing
+static_assert(pick_vec(12, 2, 0, {8}) == 1 && pick_vec(16, 2, 0, {8}) == 8 && pick_vec(16, 2, 8, {8}) == 1, "nst / rkd / sp");
 
 // ---- run-time (dtype, vec) -> template arguments (host) ----------------------------------------------------------------------
 // f(TypeTag<bf16_raw>{}) or f(TypeTag<float>{}) by MOMA_DT_*; inside a generic lambda: using T = typename decltype(t)::type
@@ -289,6 +289,14 @@ hipError_t launch_rkd_terms(const double* S_s, const double* S_t, int B, double 
                             float* loss, hipStream_t st);
 hipError_t launch_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF, int B, long long D, int dtype,
                           hipStream_t st);
+
+// ---- sp.hip (Similarity-Preserving distillation: split-K batch Gram per side, the row-normalised terms, the student's gradient) ------
+long long sp_splits(int B, long long K);
+size_t sp_workspace_bytes(int B, long long K);
+hipError_t launch_sp_gram(const void* f, int B, long long K, int dtype, float* P, hipStream_t st);
+hipError_t launch_sp_terms(const float* P_s, int splits_s, const float* P_t, int splits_t, int B, double* G, double* H, double* rows,
+                           double* M, float* loss, hipStream_t st);
+hipError_t launch_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF, int B, long long K, int dtype, hipStream_t st);
 
 // ---- infonce_fused.hip (one-pass flash-style kernel) ----------------------------------------------
 bool infonce_flash_supported(int B, int d, int K, int qdtype, int prec);

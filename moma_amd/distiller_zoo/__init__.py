@@ -2,5 +2,6 @@ from .AT import Attention
 from .KD import DistillKL
 from .NST import NSTLoss
 from .RKD import RKDLoss
+from .SP import Similarity
 
-__all__ = ["Attention", "DistillKL", "NSTLoss", "RKDLoss"]
+__all__ = ["Attention", "DistillKL", "NSTLoss", "RKDLoss", "Similarity"]

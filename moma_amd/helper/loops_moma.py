@@ -29,6 +29,11 @@ side).  Nothing to train besides the student, no memory; the step is eager.
 feature of the student's forward and of the teacher's single no-grad forward (which rides detached in the key slot, in the dtype
 autocast left it: csrc/rkd.hip reads fp32 / bf16 per side and does its arithmetic in double).  Nothing to train besides the student, no
 memory; the step is eager.
+
+`--distill similarity` (reference :140-144): the KD term is sum(Similarity([feat_s[-2]], [feat_t[-2]])) -- Similarity-Preserving
+distillation on the head map, through the same teacher branch as `attention` and `nst` (one eager no-grad forward with every feature
+map; [feat_t[-2]] rides in the key slot in the dtype and memory format the backbone left it: csrc/sp.hip reads fp32 / bf16 in storage
+order).  Nothing to train besides the student, no memory; the step is eager.
 """
 from __future__ import print_function
 
@@ -119,10 +124,10 @@ class MomaStep:
         """teacher forward #1 (:270-272), then the moma branch's no-grad part (:309-320, :327-329)."""
         opt, trainer, criterion_kd, model_t = self.opt, self.trainer, self.criterion_kd, self.model_t
         with self.autocast(), torch.no_grad():
-            if opt.distill in ("attention", "nst"):    # (:270-272, :287-292 / :150-154) every feature map, as autocast left it: an eager forward
+            if opt.distill in ("attention", "nst", "similarity"):    # (:270-272, :287-292 / :150-154 / :140-144) every feature map, as autocast left it: an eager forward
                 ft, lt = teacher(images, is_feat=True, full_feats=True) if isinstance(teacher, GraphedInference) \
                     else teacher(images, is_feat=True)
-                ft = ft[1:-1] if opt.distill == "attention" else ft[1:-2]
+                ft = ft[1:-1] if opt.distill == "attention" else ft[1:-2] if opt.distill == "nst" else [ft[-2]]
                 return lt.float(), [f.detach() for f in ft], None                # g_t rides in the key slot
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
@@ -182,6 +187,8 @@ class MomaStep:
             out["g_s"] = list(feat_s[1:-1])                                               # (:289)
         if opt.distill == "nst":
             out["g_s"] = list(feat_s[1:-2])                                               # (:151)
+        if opt.distill == "similarity":
+            out["g_s"] = [feat_s[-2]]                                                     # (:141)
         if opt.distill == "rkd":
             f_s = feat_s[-1]                                                              # (:156)
         if opt.distill == "moma":
@@ -243,7 +250,7 @@ class MomaStep:
         if opt.distill == "crd":                                                          # (:303-306) f_t rides in fw["k"]
             with self.autocast():
                 return criterion_kd(fw["f_s"], fw["k"], fw["index"], fw["contrast_idx"]).float()
-        if opt.distill in ("attention", "nst"):                                           # (:287-292 / :150-154) g_t rides in fw["k"]
+        if opt.distill in ("attention", "nst", "similarity"):                             # (:287-292 / :150-154 / :140-144) g_t rides in fw["k"]
             return sum(criterion_kd(fw["g_s"], fw["k"])).float()
         if opt.distill == "rkd":                                                          # (:155-158) f_t rides in fw["k"]
             return criterion_kd(fw["f_s"], fw["k"]).float()

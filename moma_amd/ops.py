@@ -1308,3 +1308,88 @@ def rkd_loss(f_s, f_t, w_d=25.0, w_a=50.0) -> torch.Tensor:
     if f_s.shape[0] < 2:
         raise ValueError("rkd_loss: relations need at least two rows, got B = 1")
     return _RKDLoss.apply(f_s, f_t, float(w_d), float(w_a))
+
+
+# ------------------------------------------------------------------------------------------------
+# Similarity-Preserving distillation: row-normalised batch Gram of a feature pair   (distiller_zoo/SP.py, helper/loops_moma.py:140-144)
+# ------------------------------------------------------------------------------------------------
+def sp_dense(f) -> bool:
+    """True where f [B, ...] can be read in storage order as [B, K] with row stride K: sample 0 is dense (its dimensions, in some
+    order, are contiguous) and the batch stride is K -- contiguous and channels_last tensors alike"""
+    K = 1
+    for extent, stride in sorted(((e, s) for e, s in zip(f.shape[1:], f.stride()[1:]) if e != 1), key=lambda es: es[1]):
+        if stride != K:
+            return False
+        K *= extent
+    return f.shape[0] == 1 or f.stride(0) == K
+
+
+def _sp_side(f, name):
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() < 2 or f.dtype not in _DT_CODES:
+        raise TypeError(f"sp_loss: {name} must be a float32 / bfloat16 tensor [B, ...], got {tuple(f.shape)} {f.dtype}")
+    if f.numel() == 0:
+        raise ValueError(f"sp_loss: {name} is empty: {tuple(f.shape)}")
+    if not sp_dense(f):
+        raise ValueError(f"sp_loss: {name} must be dense with the same strides in every sample (contiguous or channels_last), got "
+                         f"strides {tuple(f.stride())} for {tuple(f.shape)}")
+
+
+class _SPLoss(torch.autograd.Function):
+    """sp_gram x 2 -> sp_terms (G, H, M = Q + Q^T, loss) in the forward; sp_bwd (dF_s = g M f_s, in storage order) in the backward."""
+
+    @staticmethod
+    def forward(ctx, f_s, f_t):
+        lib = _lib.load()
+        B, dev = f_s.shape[0], f_s.device
+        Ks, Kt = f_s.numel() // B, f_t.numel() // B
+        with _timed("moma_sp_fwd"):
+            n_s, n_t = lib.moma_sp_workspace_bytes(B, Ks), lib.moma_sp_workspace_bytes(B, Kt)
+            if n_s == 0 or n_t == 0:
+                raise ValueError(f"sp_loss: the kernels take 1 .. {_lib.SP_MAX_B} rows, got {B}")
+            ws_s = torch.empty(n_s // 4, device=dev, dtype=torch.float32)
+            ws_t = torch.empty(n_t // 4, device=dev, dtype=torch.float32)
+            G = torch.empty(2, B, B, device=dev, dtype=torch.float64)
+            H = torch.empty(2, B, B, device=dev, dtype=torch.float64)
+            rows = torch.empty(4, B, device=dev, dtype=torch.float64)
+            M = torch.empty(B, B, device=dev, dtype=torch.float64)
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            check(lib.moma_sp_gram(_ptr(f_s), B, Ks, _DT_CODES[f_s.dtype], _ptr(ws_s), n_s, _stream()), "moma_sp_gram")
+            check(lib.moma_sp_gram(_ptr(f_t), B, Kt, _DT_CODES[f_t.dtype], _ptr(ws_t), n_t, _stream()), "moma_sp_gram")
+            check(lib.moma_sp_terms(_ptr(ws_s), n_s, Ks, _ptr(ws_t), n_t, Kt, B, _ptr(G), _ptr(H), _ptr(rows), _ptr(M), _ptr(loss),
+                                    _stream()), "moma_sp_terms")
+        # (sp_loss, the only caller, refuses an f_t that wants a gradient: backward runs only where f_s does, with these saved)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(f_s, M)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        f_s, M = ctx.saved_tensors
+        B = f_s.shape[0]
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        with _timed("moma_sp_bwd"):
+            dF = torch.empty_like(f_s)                # (same dtype, same strides: the storage order the kernels read)
+            if dF.stride() != f_s.stride():           # (extents of 1 may carry any stride: the input's)
+                dF = dF.as_strided(f_s.shape, f_s.stride())
+            check(lib.moma_sp_bwd(_ptr(f_s), _ptr(M), _ptr(g), _ptr(dF), B, f_s.numel() // B, _DT_CODES[f_s.dtype], _stream()),
+                  "moma_sp_bwd")
+        return dF, None
+
+
+def sp_loss(f_s, f_t) -> torch.Tensor:
+    """Similarity-Preserving loss of one pair of feature batches, f_s [B, ...] and f_t [B, ...] (float32 or bfloat16, contiguous or
+    channels_last, independently per side; any sizes behind the batch; 1 <= B <= 1024) -> scalar float32:
+    mean_ij (H^t_ij - H^s_ij)^2 with H the row-normalised B x B Gram matrix of a side's flattened samples.  The maps are read in
+    storage order (the Gram matrix does not depend on the order of the columns); the gradient flows to f_s only, in f_s's strides."""
+    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
+        _sp_side(t, nm)
+    if f_t.requires_grad and torch.is_grad_enabled():
+        raise ValueError("sp_loss: the kernels give no gradient to f_t (detach it, or use distiller_zoo.Similarity.composite)")
+    if f_s.shape[0] != f_t.shape[0]:
+        raise ValueError(f"sp_loss: batch sizes {f_s.shape[0]} and {f_t.shape[0]} differ")
+    if f_s.shape[0] > _lib.SP_MAX_B:
+        raise ValueError(f"sp_loss: the kernels take 1 .. {_lib.SP_MAX_B} rows, got {f_s.shape[0]}")
+    return _SPLoss.apply(f_s, f_t)
