@@ -369,6 +369,42 @@ int moma_sp_terms(const void* workspace_s, size_t workspace_s_bytes, long long K
 int moma_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, long long K, int dtype, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PKT  Probabilistic Knowledge Transfer (`--distill pkt`) on one pair of feature rows -- replaces PKT.cosine_similarity_loss
+ *      (distiller_zoo/PKT.py: rows / (norm + eps) -> mm with the transpose -> (. + 1) / 2 -> rows / row sums per side -> mean of
+ *      T log((T + eps) / (P + eps))) and its autograd backward to f_s, without a normalised copy of either side.  For f_s [B, Ds],
+ *      f_t [B, Dt] (each side's feat[-1] flattened), eps = 1e-7, per side
+ *          G = F F^T    n_i = sqrt(G_ii)    C_ij = G_ij / ((n_i + eps)(n_j + eps))    K = (C + 1) / 2    r_i = sum_j K_ij
+ *          P_ij = K_ij / r_i (student: P, teacher: T)        loss = (1/B^2) sum_ij T_ij log((T_ij + eps) / (P_ij + eps))
+ *          U_ij = -(1/B^2) T_ij / (P_ij + eps)    s_i = sum_k U_ik P_ik    W_ij = (U_ij - s_i) / (2 r_i)    M = W + W^T
+ *          c_i = sum_j M_ij C^s_ij    M'_ij = M_ij / ((n_i + eps)(n_j + eps)) - [i = j] c_i / (n_i (n_i + eps))    dF_s = g_loss M' f_s
+ *      The diagonal term is 0 where n_i = 0: an ALL-ZERO student row gets the finite derivative of x / (|x| + eps) at 0 (the
+ *      reference's autograd returns NaN for that row).  Nothing is clamped (K may fall a few ulps below 0; P + eps stays
+ *      positive).  The gradient goes to f_s only.
+ *      f, f_s, dF_s: MOMA_DT_F32 or MOMA_DT_BF16, rows contiguous, aligned to their element size (16-byte loads where the base
+ *      address and D allow); G, M and the workspace are double, 8-byte aligned; loss and g_loss fp32.  All arithmetic in double on
+ *      the f64 MFMA.  1 <= B <= MOMA_PKT_MAX_B (else MOMA_E_UNSUPPORTED, nothing is launched), any D >= 1.  G and M (= M' above) are
+ *      symmetric bit for bit.  No atomics: bitwise reproducible.  Three launches forward (four with one moma_pkt_gram per side), one
+ *      backward.
+ *
+ * workspace       moma_pkt_workspace_bytes(B) = (B^2 + 2 B) 8 bytes: W, one KL row sum and the student's norm per row; written and read
+ *                 by moma_pkt_terms alone.  0 for B < 1 and B > MOMA_PKT_MAX_B.
+ * moma_pkt_gram   one side: f [B, D] -> G [B, B].  Call it once for f_s and once for f_t (Ds and Dt may differ).
+ * moma_pkt_gram_pair  both sides in ONE launch (the side in the grid's third dimension): the same bits in G_s and G_t as two
+ *                 moma_pkt_gram calls.  With it the forward is three launches.
+ * moma_pkt_terms  G_s, G_t -> M [B, B] (the M' above), loss [1].
+ * moma_pkt_bwd    f_s, M -> dF_s [B, D] in f_s's dtype; g_loss is a DEVICE scalar (the upstream gradient of the loss, e.g. a GradScaler
+ *                 factor): nothing is read back to the host.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_PKT_MAX_B = 1024 };
+size_t moma_pkt_workspace_bytes(int B);
+int moma_pkt_gram(const void* f, int B, int D, int dtype, double* G, moma_stream_t stream);
+int moma_pkt_gram_pair(const void* f_s, int Ds, int dtype_s, const void* f_t, int Dt, int dtype_t, int B, double* G_s, double* G_t,
+                       moma_stream_t stream);
+int moma_pkt_terms(const double* G_s, const double* G_t, int B, void* workspace, size_t workspace_bytes, double* M, float* loss,
+                   moma_stream_t stream);
+int moma_pkt_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, int D, int dtype, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1  batch-token multi-head attention -- replaces Attention.forward
  *     (MoMA/criterion_moco_att.py:153-167) and its autograd backward.
  *     x [N,d] -> qkv = x Wqkv^T + bqkv -> per head softmax(q k^T * hd^-1/2) v -> y = a Wproj^T + bproj.

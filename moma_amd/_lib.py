@@ -17,6 +17,7 @@ LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 NST_MAX_C, NST_ROW_BLOCK = 256, 32
 RKD_MAX_B = 1024
 SP_MAX_B = 1024
+PKT_MAX_B = 1024
 MHA_SAVE_PROBS, MHA_SAVE_LSE = 0, 1
 ABI_VERSION = 4
 EMA_BLOCK_ELEMS = 4096
@@ -69,6 +70,11 @@ SIGNATURES = {
     "moma_sp_gram": (_i, [_p, _i, _l, _i, _p, _z, _p]),
     "moma_sp_terms": (_i, [_p, _z, _l, _p, _z, _l, _i, _p, _p, _p, _p, _p, _p]),
     "moma_sp_bwd": (_i, [_p, _p, _p, _p, _i, _l, _i, _p]),
+    "moma_pkt_workspace_bytes": (_z, [_i]),
+    "moma_pkt_gram": (_i, [_p, _i, _i, _i, _p, _p]),
+    "moma_pkt_gram_pair": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "moma_pkt_terms":(_i, [_p, _p, _i, _p, _z, _p, _p, _p]),
+    "moma_pkt_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "moma_mha_fwd": (_i,[_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "moma_mha_saved_state": (_i, [_i, _i, _i, _i]),
     "moma_mha_pack_bytes": (_z, [_i]),

@@ -857,4 +857,57 @@ int moma_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_
     return hip_rc(launch_sp_bwd(f_s, M, g_loss, dF_s, B, K, dtype, (hipStream_t)stream));
 }
 
+// ---- Probabilistic Knowledge Transfer ---------------------------------------------------------------------------------------------
+static int pkt_check(int B, int D, int dtype) {
+    if (B <= 0 || D <= 0) return MOMA_E_SHAPE;
+    if (bad_dt(dtype)) return MOMA_E_DTYPE;
+    if (B > MOMA_PKT_MAX_B) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_pkt_workspace_bytes(int B) {
+    if (B < 1 || B > MOMA_PKT_MAX_B) return 0;
+    return pkt_workspace_bytes(B);
+}
+
+int moma_pkt_gram(const void* f, int B, int D, int dtype, double* G, moma_stream_t stream) {
+    if (!f || !G) return MOMA_E_NULL;
+    const int rc = pkt_check(B, D, dtype);
+    if (rc != MOMA_OK) return rc;
+    if (misaligned(f, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(G, 8)) return MOMA_E_ALIGN;
+    return hip_rc(launch_pkt_gram(f, B, D, dtype, G, (hipStream_t)stream));
+}
+
+int moma_pkt_gram_pair(const void* f_s, int Ds, int dtype_s, const void* f_t, int Dt, int dtype_t, int B, double* G_s, double* G_t,
+                       moma_stream_t stream) {
+    if (!f_s || !f_t || !G_s || !G_t) return MOMA_E_NULL;
+    int rc = pkt_check(B, Ds, dtype_s);
+    if (rc == MOMA_OK) rc = pkt_check(B, Dt, dtype_t);
+    if (rc != MOMA_OK) return rc;
+    if (misaligned(f_s, dtype_s == MOMA_DT_BF16 ? 2 : 4) || misaligned(f_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(G_s, 8) ||
+        misaligned(G_t, 8))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_pkt_gram_pair(f_s, Ds, dtype_s, f_t, Dt, dtype_t, B, G_s, G_t, (hipStream_t)stream));
+}
+
+int moma_pkt_terms(const double* G_s, const double* G_t, int B, void* workspace, size_t workspace_bytes, double* M, float* loss,
+                   moma_stream_t stream) {
+    if (!G_s || !G_t || !workspace || !M || !loss) return MOMA_E_NULL;
+    const int rc = pkt_check(B, 1, MOMA_DT_F32);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < pkt_workspace_bytes(B)) return MOMA_E_WORKSPACE;
+    if (misaligned(G_s, 8) || misaligned(G_t, 8) || misaligned(workspace, 8) || misaligned(M, 8) || misaligned(loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_pkt_terms(G_s, G_t, B, workspace, M, loss, (hipStream_t)stream));
+}
+
+int moma_pkt_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, int D, int dtype, moma_stream_t stream) {
+    if (!f_s || !M || !g_loss || !dF_s) return MOMA_E_NULL;
+    const int rc = pkt_check(B, D, dtype);
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(M, 8) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_pkt_bwd(f_s, M, g_loss, dF_s, B, D, dtype, (hipStream_t)stream));
+}
+
 }  // extern "C"

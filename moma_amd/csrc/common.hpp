@@ -298,6 +298,15 @@ hipError_t launch_sp_terms(const float* P_s, int splits_s, const float* P_t, int
                            double* M, float* loss, hipStream_t st);
 hipError_t launch_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF, int B, long long K, int dtype, hipStream_t st);
 
+// ---- pkt.hip (Probabilistic Knowledge Transfer: the raw batch Gram per side in double, the cosine / KL terms, the student's gradient) --
+size_t pkt_workspace_bytes(int B);
+hipError_t launch_pkt_gram(const void* f, int B, long long D, int dtype, double* G, hipStream_t st);
+hipError_t launch_pkt_gram_pair(const void* f_s, long long Ds, int dt_s, const void* f_t, long long Dt, int dt_t, int B, double* G_s,
+                                double* G_t, hipStream_t st);
+hipError_t launch_pkt_terms(const double* G_s, const double* G_t, int B, void* ws, double* M, float* loss, hipStream_t st);
+hipError_t launch_pkt_bwd(const void* f_s, const double* M, const float* g_loss, void* dF, int B, long long D, int dtype,
+                          hipStream_t st);
+
 // ---- infonce_fused.hip (one-pass flash-style kernel) ----------------------------------------------
 bool infonce_flash_supported(int B, int d, int K, int qdtype, int prec);
 size_t infonce_flash_workspace_bytes(int B, int d, int K);

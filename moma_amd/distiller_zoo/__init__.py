@@ -1,7 +1,8 @@
 from .AT import Attention
 from .KD import DistillKL
 from .NST import NSTLoss
+from .PKT import PKT
 from .RKD import RKDLoss
 from .SP import Similarity
 
-__all__ = ["Attention", "DistillKL", "NSTLoss", "RKDLoss", "Similarity"]
+__all__ = ["Attention", "DistillKL", "NSTLoss", "PKT", "RKDLoss", "Similarity"]

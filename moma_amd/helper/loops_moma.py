@@ -34,6 +34,11 @@ memory; the step is eager.
 distillation on the head map, through the same teacher branch as `attention` and `nst` (one eager no-grad forward with every feature
 map; [feat_t[-2]] rides in the key slot in the dtype and memory format the backbone left it: csrc/sp.hip reads fp32 / bf16 in storage
 order).  Nothing to train besides the student, no memory; the step is eager.
+
+`--distill pkt` (reference :159-162): the KD term is PKT(feat_s[-1], feat_t[-1]) -- Probabilistic Knowledge Transfer on the last
+feature, through the same teacher branch as `rkd` (feat_t[-1] rides detached in the key slot, in the dtype autocast left it:
+csrc/pkt.hip reads fp32 / bf16 per side and does its arithmetic in double).  Nothing to train besides the student, no memory; the
+step is eager.
 """
 from __future__ import print_function
 
@@ -132,7 +137,7 @@ class MomaStep:
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
             return lt.float(), ft[-1].float(), None
-        if opt.distill == "rkd":          # (:155-158) likewise, as autocast left it
+        if opt.distill in ("rkd", "pkt"): # (:155-158 / :159-162) likewise, as autocast left it
             return lt.float(), ft[-1].detach(), None
         if opt.distill != "moma":
             return lt.float(), None, None
@@ -191,6 +196,8 @@ class MomaStep:
             out["g_s"] = [feat_s[-2]]                                                     # (:141)
         if opt.distill == "rkd":
             f_s = feat_s[-1]                                                              # (:156)
+        if opt.distill == "pkt":
+            f_s = feat_s[-1]                                                              # (:160)
         if opt.distill == "moma":
             with self.autocast():
                 f_s = criterion_kd.embed_s(feat_s[-1])                                    # (:323-324)
@@ -253,6 +260,8 @@ class MomaStep:
         if opt.distill in ("attention", "nst", "similarity"):                             # (:287-292 / :150-154 / :140-144) g_t rides in fw["k"]
             return sum(criterion_kd(fw["g_s"], fw["k"])).float()
         if opt.distill == "rkd":                                                          # (:155-158) f_t rides in fw["k"]
+            return criterion_kd(fw["f_s"], fw["k"]).float()
+        if opt.distill == "pkt":                                                          # (:159-162) likewise
             return criterion_kd(fw["f_s"], fw["k"]).float()
         if opt.distill != "moma":
             raise NotImplementedError(opt.distill)

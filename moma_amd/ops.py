@@ -1393,3 +1393,77 @@ def sp_loss(f_s, f_t) -> torch.Tensor:
     if f_s.shape[0] > _lib.SP_MAX_B:
         raise ValueError(f"sp_loss: the kernels take 1 .. {_lib.SP_MAX_B} rows, got {f_s.shape[0]}")
     return _SPLoss.apply(f_s, f_t)
+
+
+# ------------------------------------------------------------------------------------------------
+# Probabilistic Knowledge Transfer: cosine Gram of a batch as row distributions, their KL   (distiller_zoo/PKT.py, helper/loops_moma.py:159-162)
+# ------------------------------------------------------------------------------------------------
+def _pkt_side(f, name):
+    """-> [B, D] view of a contiguous [B, D] or [B, C, 1, 1] (any [B, ...]) float32 / bfloat16 device tensor"""
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() < 2 or f.dtype not in _DT_CODES:
+        raise TypeError(f"pkt_loss: {name} must be a float32 / bfloat16 tensor [B, ...], got {tuple(f.shape)} {f.dtype}")
+    return f.contiguous().view(f.shape[0], -1)
+
+
+class _PKTLoss(torch.autograd.Function):
+    """pkt_gram_pair (both sides, one launch) -> pkt_terms (M with dF_s = g M f_s, loss; two launches) in the forward; pkt_bwd in the
+    backward: one."""
+
+    @staticmethod
+    def forward(ctx, f_s, f_t):
+        lib = _lib.load()
+        shape = f_s.shape
+        x, y = _pkt_side(f_s, "f_s"), _pkt_side(f_t, "f_t")
+        B, dev = x.shape[0], x.device
+        with _timed("moma_pkt_fwd"):
+            n = lib.moma_pkt_workspace_bytes(B)
+            if n == 0:
+                raise ValueError(f"pkt_loss: the kernels take 1 .. {_lib.PKT_MAX_B} rows, got {B}")
+            G = torch.empty(2, B, B, device=dev, dtype=torch.float64)
+            M = torch.empty(B, B, device=dev, dtype=torch.float64)
+            ws = torch.empty(n // 8, device=dev, dtype=torch.float64)
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            check(lib.moma_pkt_gram_pair(_ptr(x), x.shape[1], _DT_CODES[x.dtype], _ptr(y), y.shape[1], _DT_CODES[y.dtype], B, _ptr(G[0]),
+                                         _ptr(G[1]), _stream()), "moma_pkt_gram_pair")
+            check(lib.moma_pkt_terms(_ptr(G[0]), _ptr(G[1]), B, _ptr(ws), n, _ptr(M), _ptr(loss), _stream()), "moma_pkt_terms")
+        # (pkt_loss, the only caller, refuses an f_t that wants a gradient: backward runs only where f_s does, with these saved)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, M)
+        ctx.shape, ctx.strides = shape, f_s.stride()
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, M = ctx.saved_tensors
+        B, D = x.shape
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        with _timed("moma_pkt_bwd"):
+            dF = torch.empty(ctx.shape, device=x.device, dtype=x.dtype)          # (contiguous, as the input the kernels saw)
+            if dF.stride() != ctx.strides:                                       # (extents of 1 may carry any stride: the input's)
+                dF = dF.as_strided(ctx.shape, ctx.strides)
+            check(lib.moma_pkt_bwd(_ptr(x), _ptr(M), _ptr(g), _ptr(dF), B, D, _DT_CODES[x.dtype], _stream()), "moma_pkt_bwd")
+        return dF, None
+
+
+def pkt_loss(f_s, f_t) -> torch.Tensor:
+    """Probabilistic Knowledge Transfer loss of one pair of feature batches, f_s [B, Ds] and f_t [B, Dt] (or [B, C, 1, 1]; float32
+    or bfloat16, contiguous, independently per side; 1 <= B <= 1024) -> scalar float32:
+    mean_ij T_ij log((T_ij + 1e-7) / (P_ij + 1e-7)), P and T the row-normalised (cosine + 1) / 2 matrices of the student's and the
+    teacher's batch, from the raw B x B Gram matrices in double (no normalised copy of either side).  The gradient flows to f_s only;
+    an all-zero student row gets a finite gradient (the reference's autograd: NaN)."""
+    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
+        _dev(t, nm, dtype=None, contiguous=False)
+        if t.dim() < 2:
+            raise ValueError(f"pkt_loss: {nm} must be [B, D] or [B, C, 1, 1], got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"pkt_loss: {nm} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
+    if f_t.requires_grad and torch.is_grad_enabled():
+        raise ValueError("pkt_loss: the kernels give no gradient to f_t (detach it, or use distiller_zoo.PKT.composite)")
+    if f_s.shape[0] != f_t.shape[0]:
+        raise ValueError(f"pkt_loss: batch sizes {f_s.shape[0]} and {f_t.shape[0]} differ")
+    if f_s.shape[0] > _lib.PKT_MAX_B:
+        raise ValueError(f"pkt_loss: the kernels take 1 .. {_lib.PKT_MAX_B} rows, got {f_s.shape[0]}")
+    return _PKTLoss.apply(f_s, f_t)

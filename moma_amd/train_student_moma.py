@@ -10,7 +10,9 @@ and launch lines carry over.  What differs:
     csrc/nst.hip; `--distill nst -c 1 -d 1 -b 50`), `rkd` (Relational Knowledge Distillation on the last feature:
     distiller_zoo/RKD.py on the pairwise-distance and angle kernels of csrc/rkd.hip; `--distill rkd -c 1 -d 1 -b 1`), `similarity`
     (Similarity-Preserving distillation on the head map feat[-2]: distiller_zoo/SP.py on the batch-Gram kernels of csrc/sp.hip; the
-    reference ships no launch line for it, the published one of RepDistiller is `--distill similarity -a 0 -b 3000`) and `crd` (Contrastive
+    reference ships no launch line for it, the published one of RepDistiller is `--distill similarity -a 0 -b 3000`), `pkt` (Probabilistic
+    Knowledge Transfer on the last feature: distiller_zoo/PKT.py on the cosine-Gram and KL kernels of csrc/pkt.hip; the reference
+    ships no launch line for it either, the published one of RepDistiller is `--distill pkt -a 0 -b 30000`) and `crd` (Contrastive
     Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
     `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
     built -- the other comparison criteria are out of scope (SURVEY section 2);
@@ -47,7 +49,7 @@ from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
-from .distiller_zoo import Attention, DistillKL, NSTLoss, RKDLoss, Similarity
+from .distiller_zoo import PKT, Attention, DistillKL, NSTLoss, RKDLoss, Similarity
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
 from .learning.contrast_trainer import ContrastTrainer
@@ -237,6 +239,8 @@ def build_training(opt, device):
         criterion_kd = RKDLoss()                                  # reference train_student_comparison.py:382-383: likewise
     elif opt.distill == "similarity":
         criterion_kd = Similarity()                               # reference train_student_moma.py:295-296: likewise
+    elif opt.distill == "pkt":
+        criterion_kd = PKT()                                      # reference train_student_comparison.py:384-385: likewise
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
