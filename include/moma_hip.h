@@ -538,6 +538,22 @@ int moma_dwconv_bwd_weight_pre(const void* x, const void* dy, float* dw, void* w
                                int act, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PW  weight gradient of a pointwise (1 x 1, stride 1, no padding, groups 1) convolution on NCHW activations -- the MBConv
+ *     `_expand_conv` / `_project_conv` / `_se_reduce` / `_se_expand` layers and `_conv_head` of the backbones inside the step
+ *     (models/efficientnet_pytorch/model.py, MBConvBlock).  A throughput helper like BN / DW: replaces MIOpen's transpose -> fill ->
+ *     split-K product -> cast chain with one read of both operands as they lie.
+ *       dw[co, ci] = sum_{n, p} dy[n, co, p] * x[n, ci, p]
+ *     x [N, Cin, HW], dy [N, Cout, HW], dw [Cout, Cin]: dense, MOMA_DT_BF16, aligned to 2 bytes (16- and 8-byte loads where the
+ *     addresses and HW allow, element loads otherwise).  MOMA_DT_F32 is answered with MOMA_E_DTYPE: the caller keeps its stock
+ *     path for fp32.  HW = 1 (the squeeze-excite layers) is the same call.  Products are exact in fp32 (bf16-input MFMA);
+ *     K = N HW is split over workgroups, the fp32 partials go to the workspace (moma_pwconv_workspace_bytes(), 16-byte
+ *     aligned) and are added in the order of the splits, then rounded once to bf16.  No atomics: bitwise reproducible.
+ * ------------------------------------------------------------------------------------------- */
+size_t moma_pwconv_workspace_bytes(int N, int Cin, int Cout, int HW);
+int moma_pwconv_bwd_weight(const void* x, const void* dy, void* dw, void* workspace, size_t workspace_bytes, int N, int Cin,
+                           int Cout, int HW, int dtype, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SE  squeeze-excite helpers on NCHW activations (models/efficientnet_pytorch/model.py:104-110):
  *     moma_plane_mean     mean[n,c] = mean_hw x[n,c,:,:]                       (F.adaptive_avg_pool2d(x, 1))
  *     moma_se_gate_fwd    out = x * sigmoid(s[n,c])                            (torch.sigmoid(x_squeezed) * x)

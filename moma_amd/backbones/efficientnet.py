@@ -34,6 +34,11 @@ _SE_MODE = os.environ.get("MOMA_SE", "hip")
 #                           prologue inside backward-weight costs more than the apply pass it removes);
 #                           0 = the two calls everywhere.
 _BNDW_FUSE = os.environ.get("MOMA_BNDW", "1")
+#   pointwise (1 x 1) convolutions: MOMA_PW=hip (default) = where the bf16 weight cache is live, the weight gradient runs on the
+#                           library's split-K MFMA kernel (pwconv.hip: one read of x and dy as they lie in NCHW, bitwise
+#                           reproducible); forward and input gradient stay MIOpen's strided GEMMs.  "miopen" = MIOpen in all
+#                           three directions (its weight-gradient solver transposes both operands into an NHWC workspace).
+_PW_MODE = os.environ.get("MOMA_PW", "hip")
 
 # (repeats, kernel, stride, expand, cin, cout, se_ratio) -- EfficientNet-B0 stage table
 _B0_STAGES = [
@@ -121,6 +126,14 @@ class SamePadConv2d(nn.Conv2d):
     def _is_depthwise(self):
         return self.groups > 1 and self.groups == self.in_channels == self.out_channels and self.bias is None
 
+    def _is_pointwise(self):
+        return (self.kernel_size == (1, 1) and self.stride == (1, 1) and self.dilation == (1, 1) and self.groups == 1
+                and self.padding == (0, 0))
+
+    def _takes_pwconv(self, is_cuda, dtype):
+        """Whether a call on an input of this device kind and dtype goes through ops.pwconv (asked without a device)."""
+        return _PW_MODE == "hip" and self._wc_live and is_cuda and dtype == torch.bfloat16 and self._is_pointwise()
+
     def forward(self, x):
         ih, iw = x.shape[-2:]
         kh, kw = self.kernel_size
@@ -147,6 +160,9 @@ class SamePadConv2d(nn.Conv2d):
                 torch.get_autocast_dtype("cuda") == torch.bfloat16:
             x = x.to(torch.bfloat16)
         w, b = self._params(x)
+        if self._takes_pwconv(x.is_cuda, x.dtype) and torch.is_grad_enabled() and w.requires_grad:
+            from .. import ops
+            return ops.pwconv(x, w, b)
         return F.conv2d(x, w, b, self.stride, pad, self.dilation, self.groups)
 
 

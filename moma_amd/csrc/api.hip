@@ -581,6 +581,24 @@ int moma_dwconv_bwd_weight_pre(const void* x, const void* dy, float* dw, void* w
                                        stride, pad_top, pad_left, dtype, scale_shift, act, (hipStream_t)stream));
 }
 
+static bool pw_bad_shape(int N, int Cin, int Cout, int HW) {
+    return N <= 0 || Cin <= 0 || Cout <= 0 || HW <= 0 || Cin > 65536 || Cout > 65536 || (long)N * HW > 0x7fffffffL;
+}
+
+size_t moma_pwconv_workspace_bytes(int N, int Cin, int Cout, int HW) {
+    return pw_bad_shape(N, Cin, Cout, HW) ? 0 : align_up(pwconv_workspace_floats(N, Cin, Cout, HW) * sizeof(float), 256);
+}
+
+int moma_pwconv_bwd_weight(const void* x, const void* dy, void* dw, void* workspace, size_t workspace_bytes, int N, int Cin,
+                           int Cout, int HW, int dtype, moma_stream_t stream) {
+    if (!x || !dy || !dw || !workspace) return MOMA_E_NULL;
+    if (pw_bad_shape(N, Cin, Cout, HW)) return MOMA_E_SHAPE;
+    if (dtype != MOMA_DT_BF16) return MOMA_E_DTYPE;          // (MOMA_DT_F32 included: the caller keeps its stock path for fp32)
+    if (misaligned(x, 2) || misaligned(dy, 2) || misaligned(dw, 2) || misaligned(workspace, 16)) return MOMA_E_ALIGN;
+    if (workspace_bytes < moma_pwconv_workspace_bytes(N, Cin, Cout, HW)) return MOMA_E_WORKSPACE;
+    return hip_rc(launch_pw_bwd_weight(x, dy, dw, (float*)workspace, N, Cin, Cout, HW, (hipStream_t)stream));
+}
+
 static int se_check(int NC, int HW, int dtype) {
     if (NC <= 0 || HW <= 0) return MOMA_E_SHAPE;
     if (dtype != MOMA_DT_F32 && dtype != MOMA_DT_BF16) return MOMA_E_DTYPE;

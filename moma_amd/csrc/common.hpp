@@ -372,6 +372,11 @@ hipError_t launch_dw_bwd_weight(const void* x, const void* dy, float* dw, float*
                                 int W, int OH, int OW, int K, int S, int pt, int pl, int dtype, const float* scale_shift, int act,
                                 hipStream_t st);
 
+// ---- pwconv.hip (pointwise convolution, NCHW: the weight gradient as a split-K bf16 MFMA product) ---------
+size_t pwconv_workspace_floats(int N, int Cin, int Cout, int HW);
+hipError_t launch_pw_bwd_weight(const void* x, const void* dy, void* dw, float* ws, int N, int Cin, int Cout, int HW,
+                                hipStream_t st);
+
 // ---- se.hip (squeeze-excite: per-plane mean, sigmoid gate) ----------------------------------------------
 hipError_t launch_plane_mean(const void* x, void* out, int NC, int HW, int dtype, hipStream_t st);
 hipError_t launch_se_gate_fwd(const void* x, const void* s, void* out, int NC, int HW, int dtype, hipStream_t st);

@@ -780,6 +780,72 @@ def dwconv(x, weight, stride: int, pad_top: int, pad_left: int, out_h: int, out_
 
 
 # ------------------------------------------------------------------------------------------------
+# Pointwise (1 x 1) convolution on NCHW activations: stock forward and input gradient, the weight gradient on the library's
+# split-K MFMA kernel (backbone helper, include/moma_hip.h "PW")
+# ------------------------------------------------------------------------------------------------
+def pwconv_native(N: int, Cin: int, Cout: int, HW: int) -> bool:
+    """Shape classes whose weight gradient the native kernel takes; the others keep MIOpen's solver.  By the layer table of
+    DESIGN.md 5a (profiles/pw_layer_microbench.txt): planes whose rows allow 8- or 16-byte loads (HW a multiple of 4: 112^2 ..
+    14^2) and the 1 x 1 planes of the squeeze-excite layers win 1.3 - 4 x; the 7 x 7 layers (49-pixel rows, 2-byte aligned:
+    element loads) lose 2.5 - 4.5 x and stay with MIOpen."""
+    return HW == 1 or HW % 4 == 0
+
+
+def pwconv_bwd_weight(x, dy):
+    """dw [Cout, Cin, 1, 1] bf16 = sum over images and pixels of dy (x) x for x [N, Cin, H, W], dy [N, Cout, H, W] (bf16, any
+    strides: both are made dense NCHW).  Bitwise reproducible; no host synchronisation (safe under graph capture)."""
+    lib = _lib.load()
+    _dev(x, "x", dtype=torch.bfloat16, contiguous=False)
+    _dev(dy, "dy", dtype=torch.bfloat16, contiguous=False)
+    if x.dim() != 4 or dy.dim() != 4 or x.shape[0] != dy.shape[0] or x.shape[2:] != dy.shape[2:]:
+        raise ValueError(f"pwconv_bwd_weight: x {tuple(x.shape)}, dy {tuple(dy.shape)}")
+    x = x.contiguous()
+    dy = dy.contiguous()
+    N, Cin, H, W = x.shape
+    Cout = dy.shape[1]
+    dw = torch.empty(Cout, Cin, 1, 1, device=x.device, dtype=torch.bfloat16)
+    ws = torch.empty(lib.moma_pwconv_workspace_bytes(N, Cin, Cout, H * W), device=x.device, dtype=torch.uint8)
+    check(lib.moma_pwconv_bwd_weight(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel(), N, Cin, Cout, H * W, DT_BF16, _stream()),
+          "moma_pwconv_bwd_weight")
+    return dw
+
+
+class _PWConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _dev(x, "x", dtype=torch.bfloat16, contiguous=False)
+        _dev(w, "weight", dtype=torch.bfloat16, contiguous=False)
+        if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[1] or w.shape[2:] != (1, 1):
+            raise ValueError(f"pwconv: x {tuple(x.shape)}, weight {tuple(w.shape)}")
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        return torch.nn.functional.conv2d(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                                     [True, False, False])[0]
+        if ctx.needs_input_grad[1]:
+            N, Cin, H, W = x.shape
+            if pwconv_native(N, Cin, w.shape[0], H * W):
+                dw = pwconv_bwd_weight(x, dy)
+            else:
+                dw = torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                                         [False, True, False])[1]
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = dy.sum((0, 2, 3))
+        return dx, dw, db
+
+
+def pwconv(x, w, b=None):
+    """conv2d with a [Cout, Cin, 1, 1] weight (stride 1, no padding) on bf16 NCHW activations."""
+    return _PWConv.apply(x, w, b)
+
+
+# ------------------------------------------------------------------------------------------------
 # BatchNorm2d + activation applied INSIDE the depthwise convolution that consumes it (the _bn0 -> _depthwise_conv
 # pair of an MBConv block): the activation tensor between the two is never written
 # ------------------------------------------------------------------------------------------------
