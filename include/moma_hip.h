@@ -505,6 +505,35 @@ int moma_bn_prepare(const void* x, const float* gamma, const float* beta, float*
                     float* running_var, float* save_mean, float* save_invstd, float* scale_shift,
                     void* workspace, size_t workspace_bytes, int N, int C, int HW, int dtype, int training,
                     float momentum, float eps, moma_stream_t stream);
+/*     BN + activation applied inside the squeeze-excite gate that consumes it (the _bn1 -> SE pair of an MBConv block):
+ *     a = act(BN(x)) is neither written nor kept.  All tensors as above; pooled, s, ds, dpooled: [N*C] of the activation dtype.
+ *       moma_bn_act_mean       the statistics and finalize of moma_bn_prepare (save_*, running_*, scale_shift [C][2], same
+ *                              workspace) and pooled[n,c] = mean_hw a[n,c,:] from one read-only pass: pooled, the saved and the
+ *                              running statistics are bit-identical to moma_bn_fwd(..., plane_mean)
+ *       moma_bn_act_gate_fwd   out = round(a) * sigmoid(s[n,c]), a rounded to the activation dtype first: bit-identical to
+ *                              moma_se_gate_fwd on the a that moma_bn_fwd stores
+ *       moma_bn_gate_bwd_sums  one pass over (x, dout = d out): five sums per plane (double) into the workspace, and from the
+ *                              fifth ds[n,c] = sigmoid'(s) * sum_hw dout * round(a) (ds nullable); from the other four ...
+ *       moma_bn_gate_bwd       ... forms dgamma, dbeta (nullable) per channel once dpooled (nullable: the gradient of pooled) is
+ *                              known, and writes dx (nullable) = BN's input gradient for
+ *                              dy = (dout * sigmoid(s) + dpooled / HW) * act'(y); training as in moma_bn_bwd
+ *     The two backward calls share ONE workspace >= moma_bn_gate_workspace_bytes(N, C), 16-byte aligned, untouched in between.
+ *     No atomics: bitwise reproducible.  (The vector width of the read-only pass follows x's alignment alone; moma_bn_fwd's
+ *     follows x and out: pooled has moma_bn_fwd's bits where out is aligned as x is, e.g. both to 32 bytes.) */
+size_t moma_bn_gate_workspace_bytes(int N, int C);
+int moma_bn_act_mean(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                     float* save_mean, float* save_invstd, float* scale_shift, void* pooled, void* workspace,
+                     size_t workspace_bytes, int N, int C, int HW, int dtype, int act, int training, float momentum,
+                     float eps, moma_stream_t stream);
+int moma_bn_act_gate_fwd(const void* x, const float* scale_shift, const void* s, void* out, int N, int C, int HW,
+                         int dtype, int act, moma_stream_t stream);
+int moma_bn_gate_bwd_sums(const void* x, const void* dout, const void* s, const float* scale_shift,
+                          const float* save_mean, const float* save_invstd, void* ds, void* workspace,
+                          size_t workspace_bytes, int N, int C, int HW, int dtype, int act, moma_stream_t stream);
+int moma_bn_gate_bwd(const void* x, const void* dout, const void* s, const void* dpooled, const float* scale_shift,
+                     const float* save_mean, const float* save_invstd, void* dx, float* dgamma, float* dbeta,
+                     void* workspace, size_t workspace_bytes, int N, int C, int HW, int dtype, int act, int training,
+                     moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * DW  depthwise convolution (groups == channels) on NCHW activations -- the MBConv `_depthwise_conv`

@@ -97,6 +97,11 @@ SIGNATURES = {
     "moma_bn_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p]),
     "moma_bn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _p, _p]),
     "moma_bn_prepare": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "moma_bn_gate_workspace_bytes": (_z, [_i, _i]),
+    "moma_bn_act_mean": (_i, [_p] * 10 + [_z] + [_i] * 6 + [_f, _f, _p]),
+    "moma_bn_act_gate_fwd": (_i, [_p] * 4 + [_i] * 5 + [_p]),
+    "moma_bn_gate_bwd_sums": (_i, [_p] * 8 + [_z] + [_i] * 5 + [_p]),
+    "moma_bn_gate_bwd": (_i, [_p] * 11 + [_z] + [_i] * 6 + [_p]),
     "moma_mha_bwd_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "moma_mha_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
 }

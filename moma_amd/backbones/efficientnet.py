@@ -39,6 +39,14 @@ _BNDW_FUSE = os.environ.get("MOMA_BNDW", "1")
 #                           reproducible); forward and input gradient stay MIOpen's strided GEMMs.  "miopen" = MIOpen in all
 #                           three directions (its weight-gradient solver transposes both operands into an NHWC workspace).
 _PW_MODE = os.environ.get("MOMA_PW", "hip")
+#   _bn1 + SiLU -> SE gate : MOMA_SEFUSE=1 (default) = where MOMA_BN and MOMA_SE both take their hip paths, BN1 + SiLU is applied inside
+#                           the gate, forward and backward (ops.bn_act_mean / ops.bn_act_gate, bnse.hip): the activation between
+#                           the two is neither written, read back nor kept for the backward -- one pass over the depthwise
+#                           output less per forward, three less per backward, bit-identical forward -- on the plane sizes at which
+#                           that was measured faster (ops.bn_se_native: 56 x 56 and up, 28 x 28 and up where a gradient is
+#                           recorded; the small planes keep the two calls); "all" = on every plane size;
+#                           "nograd" = as 1, but only in forwards that record no gradient; 0 = the two calls everywhere.
+_SE_FUSE = os.environ.get("MOMA_SEFUSE", "1")
 
 # (repeats, kernel, stride, expand, cin, cout, se_ratio) -- EfficientNet-B0 stage table
 _B0_STAGES = [
@@ -254,6 +262,28 @@ class MBConvBlock(nn.Module):
         return ops.bn_act_dwconv(e, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch, bn.momentum, bn.eps, "silu",
                                  dw.weight, sh, ph // 2, pw // 2, math.ceil(ih / sh), math.ceil(iw / sw))
 
+    def _bn1_se(self, d):
+        """se_gate(_bn1(d) + SiLU, s(pooled)) without the activation tensor (ops.bn_act_mean / ops.bn_act_gate around the unchanged
+        squeeze-excite convolutions) under exactly the conditions under which BOTH the BatchNorm and the gate would take their hip
+        paths; None otherwise.  The mode switches are read at call time."""
+        bn = self._bn1
+        if not (_SE_FUSE in ("1", "all", "nograd") and _BN_MODE == "hip" and _SE_MODE == "hip" and d.is_cuda
+                and d.dtype in (torch.float32, torch.bfloat16) and d.dim() == 4 and bn.momentum is not None):
+            return None
+        records = torch.is_grad_enabled() and (
+            d.requires_grad or any(p.requires_grad for m in (bn, self._se_reduce, self._se_expand) for p in m.parameters()))
+        if _SE_FUSE == "nograd" and records:
+            return None
+        from .. import ops
+        if _SE_FUSE != "all" and not ops.bn_se_native(d.shape[2] * d.shape[3], records):
+            return None
+        use_batch = bn.training or bn.running_mean is None
+        if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn._nbt_pending += 1
+        pooled, link = ops.bn_act_mean(d, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch, bn.momentum, bn.eps, "silu")
+        s = self._se_expand(F.silu(self._se_reduce(pooled)))
+        return ops.bn_act_gate(d, link, s)
+
     def forward(self, x, drop_connect_rate=None):
         inp = x
         d = None
@@ -264,13 +294,15 @@ class MBConvBlock(nn.Module):
                 x = self._bn0(x, act="silu")
         if d is None:
             d = self._depthwise_conv(x)
-        x, pooled = self._bn1(d, act="silu", want_mean=True)      # squeeze fused into the BN pass
-        s = self._se_expand(F.silu(self._se_reduce(pooled)))
-        if _SE_MODE == "hip" and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16):
-            from .. import ops
-            x = ops.se_gate(x, s)
-        else:
-            x = torch.sigmoid(s) * x
+        x = self._bn1_se(d)
+        if x is None:
+            x, pooled = self._bn1(d, act="silu", want_mean=True)      # squeeze fused into the BN pass
+            s = self._se_expand(F.silu(self._se_reduce(pooled)))
+            if _SE_MODE == "hip" and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16):
+                from .. import ops
+                x = ops.se_gate(x, s)
+            else:
+                x = torch.sigmoid(s) * x
         x = self._bn2(self._project_conv(x))
         if self.stride == 1 and self.cin == self.cout:
             x = _drop_connect(x, drop_connect_rate, self.training) + inp

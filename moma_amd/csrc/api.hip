@@ -515,6 +515,62 @@ int moma_bn_bwd(const void* x, const void* dout, const float* gamma, const float
                                 C, HW, dtype, act, training, dplane_mean, (hipStream_t)stream));
 }
 
+// ---- BN + activation inside the squeeze-excite gate (bnse.hip) --------------------------------------------------------------
+size_t moma_bn_gate_workspace_bytes(int N, int C) {
+    return (N > 0 && C > 0 && (long)N * C <= 0x7fffffffL / 4) ? align_up(bn_gate_workspace_floats(N, C) * sizeof(float), 256) : 0;
+}
+
+static int bn_gate_check(int N, int C, int HW, int dtype, int act, const void* ws, size_t ws_bytes) {
+    if (N <= 0 || C <= 0 || HW <= 0 || (long)N * C > 0x7fffffffL / 4 || (long)N * HW > 0x7fffffffL) return MOMA_E_SHAPE;
+    if (dtype != MOMA_DT_F32 && dtype != MOMA_DT_BF16) return MOMA_E_DTYPE;
+    if (act != MOMA_ACT_NONE && act != MOMA_ACT_SILU && act != MOMA_ACT_RELU) return MOMA_E_DTYPE;
+    if (!ws) return MOMA_E_NULL;
+    if (misaligned(ws, 16)) return MOMA_E_ALIGN;
+    if (ws_bytes < moma_bn_gate_workspace_bytes(N, C)) return MOMA_E_WORKSPACE;
+    return MOMA_OK;
+}
+
+int moma_bn_act_mean(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                     float* save_mean, float* save_invstd, float* scale_shift, void* pooled, void* workspace,
+                     size_t workspace_bytes, int N, int C, int HW, int dtype, int act, int training, float momentum, float eps,
+                     moma_stream_t stream) {
+    if (!x || !save_mean || !save_invstd || !scale_shift || !pooled) return MOMA_E_NULL;
+    if (!training && (!running_mean || !running_var)) return MOMA_E_NULL;
+    const int rc = bn_check(N, C, HW, dtype, act, workspace, workspace_bytes);
+    if (rc != MOMA_OK) return rc;
+    return hip_rc(launch_bn_act_mean(x, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale_shift, pooled,
+                                     (float*)workspace, N, C, HW, dtype, act, training, momentum, eps, (hipStream_t)stream));
+}
+
+int moma_bn_act_gate_fwd(const void* x, const float* scale_shift, const void* s, void* out, int N, int C, int HW, int dtype,
+                         int act, moma_stream_t stream) {
+    if (!x || !scale_shift || !s || !out) return MOMA_E_NULL;
+    if (N <= 0 || C <= 0 || HW <= 0 || (long)N * C > 0x7fffffffL) return MOMA_E_SHAPE;
+    if (dtype != MOMA_DT_F32 && dtype != MOMA_DT_BF16) return MOMA_E_DTYPE;
+    if (act != MOMA_ACT_NONE && act != MOMA_ACT_SILU && act != MOMA_ACT_RELU) return MOMA_E_DTYPE;
+    return hip_rc(launch_bn_act_gate_fwd(x, scale_shift, s, out, N, C, HW, dtype, act, (hipStream_t)stream));
+}
+
+int moma_bn_gate_bwd_sums(const void* x, const void* dout, const void* s, const float* scale_shift, const float* save_mean,
+                          const float* save_invstd, void* ds, void* workspace, size_t workspace_bytes, int N, int C, int HW,
+                          int dtype, int act, moma_stream_t stream) {
+    if (!x || !dout || !s || !scale_shift || !save_mean || !save_invstd) return MOMA_E_NULL;
+    const int rc = bn_gate_check(N, C, HW, dtype, act, workspace, workspace_bytes);
+    if (rc != MOMA_OK) return rc;
+    return hip_rc(launch_bn_gate_bwd_sums(x, dout, s, scale_shift, save_mean, save_invstd, ds, (float*)workspace, N, C, HW, dtype,
+                                          act, (hipStream_t)stream));
+}
+
+int moma_bn_gate_bwd(const void* x, const void* dout, const void* s, const void* dpooled, const float* scale_shift,
+                     const float* save_mean, const float* save_invstd, void* dx, float* dgamma, float* dbeta, void* workspace,
+                     size_t workspace_bytes, int N, int C, int HW, int dtype, int act, int training, moma_stream_t stream) {
+    if (!x || !dout || !s || !scale_shift || !save_mean || !save_invstd) return MOMA_E_NULL;
+    const int rc = bn_gate_check(N, C, HW, dtype, act, workspace, workspace_bytes);
+    if (rc != MOMA_OK) return rc;
+    return hip_rc(launch_bn_gate_bwd(x, dout, s, dpooled, scale_shift, save_mean, save_invstd, dx, dgamma, dbeta, (float*)workspace,
+                                     N, C, HW, dtype, act, training, (hipStream_t)stream));
+}
+
 size_t moma_dwconv_workspace_bytes(int C, int K) {
     return (C > 0 && K > 0) ? align_up(dwconv_workspace_floats(C, K) * sizeof(float), 256) : 0;
 }

@@ -359,6 +359,20 @@ hipError_t launch_bn_bwd(const void* x, const void* dout, const float* gamma, co
                          const float* save_invstd, void* dx, float* dgamma, float* dbeta, float* ws, int N, int C, int HW,
                          int dtype, int act, int training, const void* dplane_mean, hipStream_t st);
 
+// ---- bnse.hip (BN + activation inside the squeeze-excite gate: no materialised activation, forward and backward) ----------
+size_t bn_gate_workspace_floats(int N, int C);
+hipError_t launch_bn_act_mean(const void* x, const float* gamma, const float* beta, float* rm, float* rv, float* save_mean,
+                              float* save_invstd, float* scale_shift, void* pooled, float* ws, int N, int C, int HW, int dtype,
+                              int act, int training, float momentum, float eps, hipStream_t st);
+hipError_t launch_bn_act_gate_fwd(const void* x, const float* scale_shift, const void* s, void* out, int N, int C, int HW, int dtype,
+                                  int act, hipStream_t st);
+hipError_t launch_bn_gate_bwd_sums(const void* x, const void* dout, const void* s, const float* scale_shift, const float* save_mean,
+                                   const float* save_invstd, void* ds, float* ws, int N, int C, int HW, int dtype, int act,
+                                   hipStream_t st);
+hipError_t launch_bn_gate_bwd(const void* x, const void* dout, const void* s, const void* dpl, const float* scale_shift,
+                              const float* save_mean, const float* save_invstd, void* dx, float* dgamma, float* dbeta, float* ws,
+                              int N, int C, int HW, int dtype, int act, int training, hipStream_t st);
+
 // ---- dwconv.hip (depthwise convolution, NCHW) -----------------------------------------------------
 bool dwconv_supported(int K, int S);
 size_t dwconv_workspace_floats(int C, int K);

@@ -987,6 +987,155 @@ def se_gate(x, s):
 
 
 # ------------------------------------------------------------------------------------------------
+# BatchNorm2d + activation applied INSIDE the squeeze-excite gate that consumes it (the _bn1 -> SE pair of an MBConv
+# block, include/moma_hip.h "BN"): the activation between the two is neither written nor kept for the backward
+# ------------------------------------------------------------------------------------------------
+class _BNSELink:
+    """What bn_act_mean hands to bn_act_gate next to the scale / shift tensor, and where the gate's backward parks the gate's
+    gradient until the BatchNorm's backward (which always runs after it: the link tensor is one of its outputs) picks it up."""
+
+    __slots__ = ("act", "training", "save_mean", "save_invstd", "pending")
+
+    def __init__(self, act, training, save_mean, save_invstd):
+        self.act, self.training, self.save_mean, self.save_invstd = act, training, save_mean, save_invstd
+        self.pending = None                 # (dG, s, workspace with the plane sums)
+
+    def clear(self):
+        self.pending = None
+
+
+def _cuda_act(x, name, op):
+    _dev(x, name, dtype=None, contiguous=False)
+    if x.dim() != 4 or x.dtype not in _DT_CODES:
+        raise ValueError(f"{op}: expects [N,C,H,W] float32 / bfloat16, got {tuple(x.shape)} {x.dtype}")
+
+
+class _BNActMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d, weight, bias, running_mean, running_var, momentum, eps, meta):
+        lib = _lib.load()
+        d = d.contiguous()
+        N, Cc, H, W = d.shape
+        dev = d.device
+        scale_shift = torch.empty(Cc, 2, device=dev, dtype=torch.float32)
+        pooled = torch.empty(N, Cc, 1, 1, device=dev, dtype=d.dtype)
+        ws = torch.empty(lib.moma_bn_workspace_bytes(Cc), device=dev, dtype=torch.uint8)
+        check(lib.moma_bn_act_mean(_ptr(d), _ptr(weight), _ptr(bias), _ptr(running_mean), _ptr(running_var),
+                                   _ptr(meta.save_mean), _ptr(meta.save_invstd), _ptr(scale_shift), _ptr(pooled), _ptr(ws),
+                                   ws.numel(), N, Cc, H * W, _DT_CODES[d.dtype], meta.act, meta.training, float(momentum),
+                                   float(eps), _stream()), "moma_bn_act_mean")
+        ctx.save_for_backward(d, weight, bias, scale_shift)
+        ctx.meta = meta
+        ctx.set_materialize_grads(False)
+        return pooled, scale_shift
+
+    @staticmethod
+    def backward(ctx, dpl, _dlink):
+        lib = _lib.load()
+        d, weight, bias, scale_shift = ctx.saved_tensors
+        meta = ctx.meta
+        N, Cc, H, W = d.shape
+        dev, dt = d.device, _DT_CODES[d.dtype]
+        pending, meta.pending = meta.pending, None
+        if dpl is not None:
+            dpl = dpl.to(d.dtype).contiguous()
+        dx = torch.empty_like(d) if ctx.needs_input_grad[0] else None
+        dgamma = torch.empty(Cc, device=dev, dtype=torch.float32) if (weight is not None and ctx.needs_input_grad[1]) else None
+        dbeta = torch.empty(Cc, device=dev, dtype=torch.float32) if (bias is not None and ctx.needs_input_grad[2]) else None
+        if pending is None:
+            # the gate took no part in the loss: only the plane means carry a gradient -- the plain BatchNorm backward
+            if dpl is None:
+                return (None,) * 8
+            ws = torch.empty(lib.moma_bn_workspace_bytes(Cc), device=dev, dtype=torch.uint8)
+            check(lib.moma_bn_bwd(_ptr(d), _ptr(torch.zeros_like(d)), _ptr(weight), _ptr(bias), _ptr(meta.save_mean),
+                                  _ptr(meta.save_invstd), _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), N, Cc, H * W,
+                                  dt, meta.act, meta.training, _ptr(dpl), _stream()), "moma_bn_bwd")
+            return dx, dgamma, dbeta, None, None, None, None, None
+        dG, s, ws = pending
+        check(lib.moma_bn_gate_bwd(_ptr(d), _ptr(dG), _ptr(s), _ptr(dpl), _ptr(scale_shift), _ptr(meta.save_mean),
+                                   _ptr(meta.save_invstd), _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), N, Cc,
+                                   H * W, dt, meta.act, meta.training, _stream()), "moma_bn_gate_bwd")
+        return dx, dgamma, dbeta, None, None, None, None, None
+
+
+class _BNActGate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d, link, s, meta):
+        lib = _lib.load()
+        d = d.contiguous()
+        s_in_dtype = s.dtype
+        s = s.to(d.dtype).contiguous()
+        N, Cc, H, W = d.shape
+        out = torch.empty_like(d)
+        check(lib.moma_bn_act_gate_fwd(_ptr(d), _ptr(link), _ptr(s), _ptr(out), N, Cc, H * W, _DT_CODES[d.dtype], meta.act,
+                                       _stream()), "moma_bn_act_gate_fwd")
+        ctx.save_for_backward(d, link, s)
+        ctx.meta, ctx.s_dtype = meta, s_in_dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        d, link, s = ctx.saved_tensors
+        meta = ctx.meta
+        N, Cc, H, W = d.shape
+        dout = dout.contiguous()
+        if dout.dtype != d.dtype:
+            dout = dout.to(d.dtype)
+        ds = torch.empty_like(s) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(lib.moma_bn_gate_workspace_bytes(N, Cc), device=d.device, dtype=torch.uint8)
+        check(lib.moma_bn_gate_bwd_sums(_ptr(d), _ptr(dout), _ptr(s), _ptr(link), _ptr(meta.save_mean), _ptr(meta.save_invstd),
+                                        _ptr(ds), _ptr(ws), ws.numel(), N, Cc, H * W, _DT_CODES[d.dtype], meta.act, _stream()),
+              "moma_bn_gate_bwd_sums")
+        dlink = None
+        if ctx.needs_input_grad[1]:
+            # the BatchNorm's backward finishes the job (dD comes out once, there, with the gradient of the plane means folded in);
+            # the link's "gradient" only makes autograd run it: a zero-stride view, its values are never read
+            meta.pending = (dout, s, ws)
+            # should this pass never reach the BatchNorm's node (a gradient asked of s alone), nothing stays parked behind it
+            torch.autograd.Variable._execution_engine.queue_callback(meta.clear)
+            dlink = meta.save_mean[:1].expand(Cc, 2)
+        if ds is not None and ds.dtype != ctx.s_dtype:
+            ds = ds.to(ctx.s_dtype)
+        return None, dlink, ds, None
+
+
+def bn_se_native(HW: int, records_grad: bool) -> bool:
+    """Plane sizes at which an MBConv block takes the fused pair below instead of bn_act + se_gate.  By the layer table of
+    DESIGN.md 5a (profiles/bnse_layer_microbench.txt, B = 256): one wave walks one plane, which streams at 3.4 - 4 TB/s on planes
+    of 56 x 56 and up (forward x 1.33 - 1.39, forward + backward x 1.34 - 1.38) and still wins forward + backward at 28 x 28
+    (x 1.06 - 1.15; the forward alone is a tie there); on the 14 x 14 and 7 x 7 planes a wave has at most one vector per lane, the
+    five wave-wide sums of the backward outweigh the passes they save (forward x 0.90 - 1.00, forward + backward x 0.77 - 0.96)
+    and the two calls stay."""
+    return HW >= (28 * 28 if records_grad else 56 * 56)
+
+
+def bn_act_mean(d, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float, act=None):
+    """The squeeze of act(batch_norm(d)) without the activation tensor: (pooled [N,C,1,1], link).  `pooled` and the running
+    statistics (updated in place when training) are those of bn_act(..., want_mean=True) bit for bit; `link` (the per-channel
+    scale / shift, [C, 2] fp32) goes to bn_act_gate together with the same d."""
+    _cuda_act(d, "d", "bn_act_mean")
+    Cc = d.shape[1]
+    meta = _BNSELink(ACT_CODES[act], int(bool(training)), torch.empty(Cc, device=d.device, dtype=torch.float32),
+                     torch.empty(Cc, device=d.device, dtype=torch.float32))
+    pooled, link = _BNActMean.apply(d, weight, bias, running_mean, running_var, momentum, eps, meta)
+    link._moma_bnse = meta
+    return pooled, link
+
+
+def bn_act_gate(d, link, s):
+    """act(batch_norm(d)) * sigmoid(s) for the (d, link) of bn_act_mean and s [N,C,1,1]: bit for bit
+    se_gate(bn_act(d, ...), s), in one pass less forward and three less backward."""
+    _cuda_act(d, "d", "bn_act_gate")
+    _dev(s, "s", dtype=None, contiguous=False)
+    meta = getattr(link, "_moma_bnse", None)
+    if meta is None or s.numel() != d.shape[0] * d.shape[1] or tuple(link.shape) != (d.shape[1], 2):
+        raise ValueError(f"bn_act_gate: d {tuple(d.shape)}, s {tuple(s.shape)}, link {tuple(link.shape)} (from bn_act_mean: "
+                         f"{meta is not None})")
+    return _BNActGate.apply(d, link, s, meta)
+
+
+# ------------------------------------------------------------------------------------------------
 # CRD: gather-contrast over two sample-indexed memory banks   (crd/memory.py:23-79, crd/criterion.py:57-74)
 # ------------------------------------------------------------------------------------------------
 def _crd_check(v1, v2, memory_v1, memory_v2, idx, n_data, Z, bad):
