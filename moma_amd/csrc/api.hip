@@ -843,13 +843,33 @@ int moma_nst_bwd(const void* f_s, const void* f_t, const void* workspace, size_t
                                  layout_t, (hipStream_t)stream));
 }
 
-// ---- Relational Knowledge Distillation ------------------------------------------------------------------------------------------
-static int rkd_check(int B, int D, int dtype) {
+// ---- The losses on a B x B batch relation (rkd, sp, pkt): the guards they share ---------------------------------------------------
+// f [B, D] of `dtype` with lo <= B <= hi
+static int rel_check(int B, long long D, int dtype, int lo, int hi) {
     if (B <= 0 || D <= 0) return MOMA_E_SHAPE;
     if (bad_dt(dtype)) return MOMA_E_DTYPE;
-    if (B < 2 || B > MOMA_RKD_MAX_B) return MOMA_E_UNSUPPORTED;
+    if (B < lo || B > hi) return MOMA_E_UNSUPPORTED;
     return MOMA_OK;
 }
+
+// f [B, D] -> a B x B matrix of doubles (moma_rkd_dist, moma_pkt_gram); rc: the entry point's shape check
+static int rel_side_guard(const void* f, const double* out, int dtype, int rc) {
+    if (!f || !out) return MOMA_E_NULL;
+    if (rc != MOMA_OK) return rc;
+    if (misaligned(f, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(out, 8)) return MOMA_E_ALIGN;
+    return MOMA_OK;
+}
+
+// dF_s from f_s, the B x B matrix M and the device scalar g_loss (the three *_bwd); rc: the entry point's shape check
+static int rel_bwd_guard(const void* f_s, const double* M, const float* g_loss, const void* dF_s, int dtype, int rc) {
+    if (!f_s || !M || !g_loss || !dF_s) return MOMA_E_NULL;
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(M, 8) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
+    return MOMA_OK;
+}
+
+// ---- Relational Knowledge Distillation ------------------------------------------------------------------------------------------
 
 size_t moma_rkd_workspace_bytes(int B) {
     if (B < 2 || B > MOMA_RKD_MAX_B) return 0;
@@ -857,17 +877,15 @@ size_t moma_rkd_workspace_bytes(int B) {
 }
 
 int moma_rkd_dist(const void* f, int B, int D, int dtype, double* S, moma_stream_t stream) {
-    if (!f || !S) return MOMA_E_NULL;
-    const int rc = rkd_check(B, D, dtype);
+    const int rc = rel_side_guard(f, S, dtype, rel_check(B, D, dtype, 2, MOMA_RKD_MAX_B));
     if (rc != MOMA_OK) return rc;
-    if (misaligned(f, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(S, 8)) return MOMA_E_ALIGN;
     return hip_rc(launch_rkd_dist(f, B, D, dtype, S, (hipStream_t)stream));
 }
 
 int moma_rkd_terms(const double* S_s, const double* S_t, int B, float w_d, float w_a, void* workspace, size_t workspace_bytes,
                    double* Q, float* terms, float* loss, moma_stream_t stream) {
     if (!S_s || !S_t || !workspace || !Q || !terms || !loss) return MOMA_E_NULL;
-    const int rc = rkd_check(B, 1, MOMA_DT_F32);
+    const int rc = rel_check(B, 1, MOMA_DT_F32, 2, MOMA_RKD_MAX_B);
     if (rc != MOMA_OK) return rc;
     if (workspace_bytes < rkd_workspace_bytes(B)) return MOMA_E_WORKSPACE;
     if (misaligned(S_s, 8) || misaligned(S_t, 8) || misaligned(workspace, 8) || misaligned(Q, 8) || misaligned(terms, 4) ||
@@ -877,19 +895,15 @@ int moma_rkd_terms(const double* S_s, const double* S_t, int B, float w_d, float
 }
 
 int moma_rkd_bwd(const void* f_s, const double* Q, const float* g_loss, void* dF_s, int B, int D, int dtype, moma_stream_t stream) {
-    if (!f_s || !Q || !g_loss || !dF_s) return MOMA_E_NULL;
-    const int rc = rkd_check(B, D, dtype);
+    const int rc = rel_bwd_guard(f_s, Q, g_loss, dF_s, dtype, rel_check(B, D, dtype, 2, MOMA_RKD_MAX_B));
     if (rc != MOMA_OK) return rc;
-    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
-    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(Q, 8) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
     return hip_rc(launch_rkd_bwd(f_s, Q, g_loss, dF_s, B, D, dtype, (hipStream_t)stream));
 }
 
 // ---- Similarity-Preserving distillation ------------------------------------------------------------------------------------------
 static int sp_check(int B, long long K, int dtype) {
-    if (B <= 0 || K <= 0) return MOMA_E_SHAPE;
-    if (bad_dt(dtype)) return MOMA_E_DTYPE;
-    if (B > MOMA_SP_MAX_B) return MOMA_E_UNSUPPORTED;
+    const int rc = rel_check(B, K, dtype, 1, MOMA_SP_MAX_B);
+    if (rc != MOMA_OK) return rc;
     if ((K + 63) / 64 > INT32_MAX) return MOMA_E_UNSUPPORTED;                    // (sp_bwd's grid)
     return MOMA_OK;
 }
@@ -923,40 +937,28 @@ int moma_sp_terms(const void* workspace_s, size_t workspace_s_bytes, long long K
 }
 
 int moma_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, long long K, int dtype, moma_stream_t stream) {
-    if (!f_s || !M || !g_loss || !dF_s) return MOMA_E_NULL;
-    const int rc = sp_check(B, K, dtype);
+    const int rc = rel_bwd_guard(f_s, M, g_loss, dF_s, dtype, sp_check(B, K, dtype));
     if (rc != MOMA_OK) return rc;
-    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
-    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(M, 8) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
     return hip_rc(launch_sp_bwd(f_s, M, g_loss, dF_s, B, K, dtype, (hipStream_t)stream));
 }
 
 // ---- Probabilistic Knowledge Transfer ---------------------------------------------------------------------------------------------
-static int pkt_check(int B, int D, int dtype) {
-    if (B <= 0 || D <= 0) return MOMA_E_SHAPE;
-    if (bad_dt(dtype)) return MOMA_E_DTYPE;
-    if (B > MOMA_PKT_MAX_B) return MOMA_E_UNSUPPORTED;
-    return MOMA_OK;
-}
-
 size_t moma_pkt_workspace_bytes(int B) {
     if (B < 1 || B > MOMA_PKT_MAX_B) return 0;
     return pkt_workspace_bytes(B);
 }
 
 int moma_pkt_gram(const void* f, int B, int D, int dtype, double* G, moma_stream_t stream) {
-    if (!f || !G) return MOMA_E_NULL;
-    const int rc = pkt_check(B, D, dtype);
+    const int rc = rel_side_guard(f, G, dtype, rel_check(B, D, dtype, 1, MOMA_PKT_MAX_B));
     if (rc != MOMA_OK) return rc;
-    if (misaligned(f, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(G, 8)) return MOMA_E_ALIGN;
     return hip_rc(launch_pkt_gram(f, B, D, dtype, G, (hipStream_t)stream));
 }
 
 int moma_pkt_gram_pair(const void* f_s, int Ds, int dtype_s, const void* f_t, int Dt, int dtype_t, int B, double* G_s, double* G_t,
                        moma_stream_t stream) {
     if (!f_s || !f_t || !G_s || !G_t) return MOMA_E_NULL;
-    int rc = pkt_check(B, Ds, dtype_s);
-    if (rc == MOMA_OK) rc = pkt_check(B, Dt, dtype_t);
+    int rc = rel_check(B, Ds, dtype_s, 1, MOMA_PKT_MAX_B);
+    if (rc == MOMA_OK) rc = rel_check(B, Dt, dtype_t, 1, MOMA_PKT_MAX_B);
     if (rc != MOMA_OK) return rc;
     if (misaligned(f_s, dtype_s == MOMA_DT_BF16 ? 2 : 4) || misaligned(f_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(G_s, 8) ||
         misaligned(G_t, 8))
@@ -967,7 +969,7 @@ int moma_pkt_gram_pair(const void* f_s, int Ds, int dtype_s, const void* f_t, in
 int moma_pkt_terms(const double* G_s, const double* G_t, int B, void* workspace, size_t workspace_bytes, double* M, float* loss,
                    moma_stream_t stream) {
     if (!G_s || !G_t || !workspace || !M || !loss) return MOMA_E_NULL;
-    const int rc = pkt_check(B, 1, MOMA_DT_F32);
+    const int rc = rel_check(B, 1, MOMA_DT_F32, 1, MOMA_PKT_MAX_B);
     if (rc != MOMA_OK) return rc;
     if (workspace_bytes < pkt_workspace_bytes(B)) return MOMA_E_WORKSPACE;
     if (misaligned(G_s, 8) || misaligned(G_t, 8) || misaligned(workspace, 8) || misaligned(M, 8) || misaligned(loss, 4))
@@ -976,11 +978,8 @@ int moma_pkt_terms(const double* G_s, const double* G_t, int B, void* workspace,
 }
 
 int moma_pkt_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, int D, int dtype, moma_stream_t stream) {
-    if (!f_s || !M || !g_loss || !dF_s) return MOMA_E_NULL;
-    const int rc = pkt_check(B, D, dtype);
+    const int rc = rel_bwd_guard(f_s, M, g_loss, dF_s, dtype, rel_check(B, D, dtype, 1, MOMA_PKT_MAX_B));
     if (rc != MOMA_OK) return rc;
-    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
-    if (misaligned(f_s, eb) || misaligned(dF_s, eb) || misaligned(M, 8) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
     return hip_rc(launch_pkt_bwd(f_s, M, g_loss, dF_s, B, D, dtype, (hipStream_t)stream));
 }
 

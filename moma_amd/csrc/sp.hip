@@ -18,9 +18,9 @@
 //             hipcc -O3, gfx950: 69 VGPRs (fp32) / 82 (bf16) + 16 AGPRs (the accumulator), no spill, no scratch; LDS 32.5 KB / 34 KB.
 //   sp_terms  three launches, all in double:
 //     sp_rows   grid B: row i of both sides: G = the split partials added in the order 0, 1, ...; n; H; r_i = E_i . H^s_i; the row's
-//               sum of (H^t - H^s)^2.                                                             52 VGPRs, LDS 32 B
+//               sum of (H^t - H^s)^2; the sums over the workgroup: block_sum of batchrel.hpp.       50 VGPRs, LDS 32 B
 //     sp_m      grid ceil(B / 16)^2: M_ij = Q_ij + Q_ji (the same sum for (i, j) and (j, i): symmetric bit for bit).   24 VGPRs
-//     sp_final  one workgroup adds the B row sums in a fixed order -> loss (fp32).                     13 VGPRs, LDS 32 B
+//     sp_final  one workgroup adds the B row sums in a fixed order (array_sum of batchrel.hpp) -> loss (fp32).   13 VGPRs, LDS 32 B
 //   sp_bwd    grid (ceil(K / 64), ceil(B / 128)): dF_s[128 rows, 64 columns] = g M X[:, 64 columns] on v_mfma_f32_32x32x2_f32 for both
 //             storages (bf16 widened while it is staged; M rounded to fp32 once per use: every workgroup reads its
 //             [128, B] block of M as double and converts it -- B^2 8 bytes of L2 reads per 64 columns, 0.5 GB at B = 256, K = 62720,
@@ -31,12 +31,11 @@
 //             hipcc -O3, gfx950: 119 VGPRs (fp32) / 106 (bf16) + 32 AGPRs (the accumulators), no spill, no scratch; LDS 16.5 KB M + 12 KB X.
 // None of the launches spills or uses scratch (the compiler's kernel-resource-usage report).
 // No atomics: every sum has an order that depends on the shapes alone -- bitwise repeatable.
-#include "common.hpp"
+#include "batchrel.hpp"
 
 namespace moma {
 namespace {
 
-constexpr int SP_THREADS = 256;
 constexpr int SP_T = 64;                     // rows / columns of a workgroup's tile of G
 constexpr int SP_TARGET = 512;               // workgroups sp_gram aims at (two per compute unit)
 constexpr int SP_TM = 16;                    // rows / columns of a tile of M
@@ -54,15 +53,6 @@ template <> struct SpSlab<bf16_raw> { static constexpr int KS = 128, LD = 136; }
 // row of accumulator register `reg` in a 32 x 32 MFMA result (the column is lane & 31)
 __device__ __forceinline__ int sp_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
-// sum over the workgroup in a fixed order (butterfly inside a wave, then waves 0, 1, 2, 3), the result in every thread
-__device__ __forceinline__ double sp_block_sum(double v, double* sh) {
-    v = wave_sum(v);
-    __syncthreads();                                              // (sh may still be read from the previous call)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 // rows [r0, r0 + 64) x columns [k0, k0 + KS) of f [B, K] -> lds[r * LD + kk] in the storage type; zero past B and past K.
 // vec: K is a multiple of the vector width and the base is 16-byte aligned (k0 is a multiple of KS)
 template <typename T>
@@ -70,7 +60,7 @@ __device__ __forceinline__ void sp_stage(const T* __restrict__ f, int B, long lo
     constexpr int KS = SpSlab<T>::KS, LD = SpSlab<T>::LD, V = MAXVEC<T>, VPR = KS / V;      // vectors per row of the slab
     const int tid = threadIdx.x;
     if (vec) {
-        for (int idx = tid; idx < SP_T * VPR; idx += SP_THREADS) {
+        for (int idx = tid; idx < SP_T * VPR; idx += REL_THREADS) {
             const int r = idx / VPR, kv = idx % VPR, row = r0 + r;
             const long long k = k0 + kv * V;
             const bool in = row < B && k < K;                                               // (K % V == 0: all V inside)
@@ -87,7 +77,7 @@ __device__ __forceinline__ void sp_stage(const T* __restrict__ f, int B, long lo
             }
         }
     } else {
-        for (int idx = tid; idx < SP_T * KS; idx += SP_THREADS) {
+        for (int idx = tid; idx < SP_T * KS; idx += REL_THREADS) {
             const int r = idx / KS, kk = idx % KS, row = r0 + r;
             const long long k = k0 + kk;
             lds[r * LD + kk] = (row < B && k < K) ? f[(size_t)row * K + k] : (T)0;
@@ -111,8 +101,8 @@ __device__ __forceinline__ void sp_slab_mma(const bf16_raw* __restrict__ xi, con
 
 // grid (nt (nt + 1) / 2, splits): tile pair blockIdx.x (ti <= tj, row by row), split blockIdx.y
 template <typename T>
-__global__ __launch_bounds__(SP_THREADS) void sp_gram_kernel(const T* __restrict__ f, float* __restrict__ P, int B, long long K, int vec,
-                                                             int nt, long long per, long long nslabs) {
+__global__ __launch_bounds__(REL_THREADS) void sp_gram_kernel(const T* __restrict__ f, float* __restrict__ P, int B, long long K, int vec,
+                                                              int nt, long long per, long long nslabs) {
     constexpr int KS = SpSlab<T>::KS, LD = SpSlab<T>::LD;
     __shared__ __attribute__((aligned(16))) T Xi[SP_T * LD];
     __shared__ __attribute__((aligned(16))) T Xj[SP_T * LD];
@@ -154,17 +144,17 @@ __global__ __launch_bounds__(SP_THREADS) void sp_gram_kernel(const T* __restrict
 }
 
 // grid B: row i of both sides.  rows = [n_s | n_t | r | lp], each [B]
-__global__ __launch_bounds__(SP_THREADS) void sp_rows_kernel(const float* __restrict__ Ps, int splits_s, const float* __restrict__ Pt,
-                                                             int splits_t, int B, double* __restrict__ G, double* __restrict__ H,
-                                                             double* __restrict__ rows) {
+__global__ __launch_bounds__(REL_THREADS) void sp_rows_kernel(const float* __restrict__ Ps, int splits_s, const float* __restrict__ Pt,
+                                                              int splits_t, int B, double* __restrict__ G, double* __restrict__ H,
+                                                              double* __restrict__ rows) {
     __shared__ double sh[4];
-    constexpr int PER = MOMA_SP_MAX_B / SP_THREADS;               // entries of a row per thread
+    constexpr int PER = MOMA_SP_MAX_B / REL_THREADS;               // entries of a row per thread
     const int i = blockIdx.x;
     const size_t BB = (size_t)B * B;
     double gs[PER], gt[PER], qs = 0.0, qt = 0.0;
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
-        const int j = threadIdx.x + u * SP_THREADS;
+        const int j = threadIdx.x + u * REL_THREADS;
         gs[u] = 0.0;
         gt[u] = 0.0;
         if (j < B) {
@@ -181,12 +171,12 @@ __global__ __launch_bounds__(SP_THREADS) void sp_rows_kernel(const float* __rest
             qt = fma(gt[u], gt[u], qt);
         }
     }
-    const double n_s = sqrt(sp_block_sum(qs, sh)), n_t = sqrt(sp_block_sum(qt, sh));
+    const double n_s = sqrt(block_sum(qs, sh)), n_t = sqrt(block_sum(qt, sh));
     const double c_s = fmax(n_s, SP_EPS), c_t = fmax(n_t, SP_EPS), e = -2.0 / ((double)B * B);
     double r = 0.0, lp = 0.0;
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
-        const int j = threadIdx.x + u * SP_THREADS;
+        const int j = threadIdx.x + u * REL_THREADS;
         if (j < B) {
             const size_t o = (size_t)i * B + j;
             const double hs = gs[u] / c_s, ht = gt[u] / c_t, d = ht - hs;
@@ -196,8 +186,8 @@ __global__ __launch_bounds__(SP_THREADS) void sp_rows_kernel(const float* __rest
             lp = fma(d, d, lp);
         }
     }
-    r = sp_block_sum(r, sh);
-    lp = sp_block_sum(lp, sh);
+    r = block_sum(r, sh);
+    lp = block_sum(lp, sh);
     if (threadIdx.x == 0) {
         rows[i] = n_s;
         rows[B + i] = n_t;
@@ -213,8 +203,8 @@ __device__ __forceinline__ double sp_q(double hs, double ht, double n, double r,
 }
 
 // grid (ceil(B / 16), ceil(B / 16)): thread (i, j)
-__global__ __launch_bounds__(SP_THREADS) void sp_m_kernel(const double* __restrict__ H, const double* __restrict__ rows, int B,
-                                                          double* __restrict__ M) {
+__global__ __launch_bounds__(REL_THREADS) void sp_m_kernel(const double* __restrict__ H, const double* __restrict__ rows, int B,
+                                                           double* __restrict__ M) {
     const int i = blockIdx.y * SP_TM + (threadIdx.x >> 4), j = blockIdx.x * SP_TM + (threadIdx.x & 15);
     if (i >= B || j >= B) return;
     const size_t BB = (size_t)B * B, ij = (size_t)i * B + j, ji = (size_t)j * B + i;
@@ -223,19 +213,17 @@ __global__ __launch_bounds__(SP_THREADS) void sp_m_kernel(const double* __restri
     M[ij] = i <= j ? a + b : b + a;                               // (the same two operands in the same order for (i, j) and (j, i))
 }
 
-__global__ __launch_bounds__(SP_THREADS) void sp_final_kernel(const double* __restrict__ lp, int B, float* __restrict__ loss) {
+__global__ __launch_bounds__(REL_THREADS) void sp_final_kernel(const double* __restrict__ lp, int B, float* __restrict__ loss) {
     __shared__ double sh[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < B; i += SP_THREADS) s += lp[i];
-    s = sp_block_sum(s, sh);
+    const double s = array_sum(lp, B, sh);
     if (threadIdx.x == 0) *loss = (float)(s / ((double)B * B));
 }
 
 // grid (ceil(K / 64), ceil(B / 128)): rows [128 by, +128) x columns [64 bx, +64) of dX
 template <typename T>
-__global__ __launch_bounds__(SP_THREADS) void sp_bwd_kernel(const T* __restrict__ X, const double* __restrict__ M,
-                                                            const float* __restrict__ g_loss, T* __restrict__ dX, int B, long long K,
-                                                            int vec) {
+__global__ __launch_bounds__(REL_THREADS) void sp_bwd_kernel(const T* __restrict__ X, const double* __restrict__ M,
+                                                             const float* __restrict__ g_loss, T* __restrict__ dX, int B, long long K,
+                                                             int vec) {
     __shared__ float Ml[SP_BR * SP_LDM];
     __shared__ float Xl[SP_BJ * SP_LDX];
     constexpr int V = MAXVEC<T>, VPR = SP_BC / V;
@@ -250,12 +238,12 @@ __global__ __launch_bounds__(SP_THREADS) void sp_bwd_kernel(const T* __restrict_
         for (int r = 0; r < 16; ++r) { acc[t][r] = 0.f; tot[t][r] = 0.0; }
     for (int j0 = 0; j0 < B; j0 += SP_BJ) {
         __syncthreads();                                          // the slab of the previous turn has been read
-        for (int idx = tid; idx < SP_BR * SP_BJ; idx += SP_THREADS) {
+        for (int idx = tid; idx < SP_BR * SP_BJ; idx += REL_THREADS) {
             const int r = idx / SP_BJ, jj = idx % SP_BJ, i = i0 + r, j = j0 + jj;
             Ml[r * SP_LDM + jj] = (i < B && j < B) ? (float)M[(size_t)i * B + j] : 0.f;
         }
         if (vec) {
-            for (int idx = tid; idx < SP_BJ * VPR; idx += SP_THREADS) {
+            for (int idx = tid; idx < SP_BJ * VPR; idx += REL_THREADS) {
                 const int jj = idx / VPR, cv = idx % VPR, j = j0 + jj;
                 const long long c = c0 + cv * V;
                 float v[V];
@@ -267,7 +255,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_bwd_kernel(const T* __restrict_
                 for (int e = 0; e < V; ++e) o[e] = v[e];
             }
         } else {
-            for (int idx = tid; idx < SP_BJ * SP_BC; idx += SP_THREADS) {
+            for (int idx = tid; idx < SP_BJ * SP_BC; idx += REL_THREADS) {
                 const int jj = idx / SP_BC, cc = idx % SP_BC, j = j0 + jj;
                 const long long c = c0 + cc;
                 Xl[jj * SP_LDX + cc] = (j < B && c < K) ? ld1<T>(X + (size_t)j * K + c) : 0.f;
@@ -323,7 +311,7 @@ hipError_t launch_sp_gram(const void* f, int B, long long K, int dtype, float* P
     return with_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         const int vec = pick_vec(K, sizeof(T), (uintptr_t)f, {MAXVEC<T>}) > 1;      // 16 bytes or nothing
-        hipLaunchKernelGGL(sp_gram_kernel<T>, grid, dim3(SP_THREADS), 0, st, (const T*)f, P, B, K, vec, nt, per, slabs);
+        hipLaunchKernelGGL(sp_gram_kernel<T>, grid, dim3(REL_THREADS), 0, st, (const T*)f, P, B, K, vec, nt, per, slabs);
         return hipGetLastError();
     });
 }
@@ -331,12 +319,12 @@ hipError_t launch_sp_gram(const void* f, int B, long long K, int dtype, float* P
 hipError_t launch_sp_terms(const float* P_s, int splits_s, const float* P_t, int splits_t, int B, double* G, double* H, double* rows,
                            double* M, float* loss, hipStream_t st) {
     const int nm = (B + SP_TM - 1) / SP_TM;
-    hipLaunchKernelGGL(sp_rows_kernel, dim3(B), dim3(SP_THREADS), 0, st, P_s, splits_s, P_t, splits_t, B, G, H, rows);
+    hipLaunchKernelGGL(sp_rows_kernel, dim3(B), dim3(REL_THREADS), 0, st, P_s, splits_s, P_t, splits_t, B, G, H, rows);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sp_m_kernel, dim3(nm, nm), dim3(SP_THREADS), 0, st, (const double*)H, (const double*)rows, B, M);
+    hipLaunchKernelGGL(sp_m_kernel, dim3(nm, nm), dim3(REL_THREADS), 0, st, (const double*)H, (const double*)rows, B, M);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(sp_final_kernel, dim3(1), dim3(SP_THREADS), 0, st, (const double*)(rows + 3 * (size_t)B), B, loss);
+    hipLaunchKernelGGL(sp_final_kernel, dim3(1), dim3(REL_THREADS), 0, st, (const double*)(rows + 3 * (size_t)B), B, loss);
     return hipGetLastError();
 }
 
@@ -345,7 +333,7 @@ hipError_t launch_sp_bwd(const void* f_s, const double* M, const float* g_loss, 
     return with_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         const int vec = (pick_vec(K, sizeof(T), (uintptr_t)f_s, {MAXVEC<T>}) > 1);  // 16 bytes or nothing
-        hipLaunchKernelGGL(sp_bwd_kernel<T>, grid, dim3(SP_THREADS), 0, st, (const T*)f_s, M, g_loss, (T*)dF, B, K, vec);
+        hipLaunchKernelGGL(sp_bwd_kernel<T>, grid, dim3(REL_THREADS), 0, st, (const T*)f_s, M, g_loss, (T*)dF, B, K, vec);
         return hipGetLastError();
     });
 }

@@ -1452,14 +1452,49 @@ def nst_loss(f_s, f_t) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
-# Relational Knowledge Distillation: pairwise distances and angles of a batch   (distiller_zoo/RKD.py, helper/loops_moma.py:155-158)
+# What the losses on a B x B batch relation (rkd, sp, pkt: below) share: guards, the [B, D] view, the backward call
 # ------------------------------------------------------------------------------------------------
-def _rkd_side(f, name):
+def _rel_side(op, f, name):
     """-> [B, D] view of a contiguous [B, D] or [B, C, 1, 1] (any [B, ...]) float32 / bfloat16 device tensor (copied when not dense)"""
     _dev(f, name, dtype=None, contiguous=False)
     if f.dim() < 2 or f.dtype not in _DT_CODES:
-        raise TypeError(f"rkd_loss: {name} must be a float32 / bfloat16 tensor [B, ...], got {tuple(f.shape)} {f.dtype}")
+        raise TypeError(f"{op}: {name} must be a float32 / bfloat16 tensor [B, ...], got {tuple(f.shape)} {f.dtype}")
     return f.contiguous().view(f.shape[0], -1)
+
+
+def _rel_contiguous_sides(op, f_s, f_t):
+    """the per-side guards of rkd_loss and pkt_loss: on the device, [B, ...] with at least two dimensions, contiguous"""
+    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
+        _dev(t, nm, dtype=None, contiguous=False)
+        if t.dim() < 2:
+            raise ValueError(f"{op}: {nm} must be [B, D] or [B, C, 1, 1], got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {nm} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
+
+
+def _rel_pair_guards(op, composite, f_s, f_t):
+    """behind the per-side guards of the three losses: no gradient to f_t, equal batch sizes"""
+    if f_t.requires_grad and torch.is_grad_enabled():
+        raise ValueError(f"{op}: the kernels give no gradient to f_t (detach it, or use distiller_zoo.{composite}.composite)")
+    if f_s.shape[0] != f_t.shape[0]:
+        raise ValueError(f"{op}: batch sizes {f_s.shape[0]} and {f_t.shape[0]} differ")
+
+
+def _rel_backward(entry, x, M, g, shape, strides):
+    """the backward of the three losses: moma_<entry>_bwd(x read as [B, numel / B], M [B, B], g) -> dF_s in x's dtype with the
+    input's shape and strides (the order the kernels read; extents of 1 may carry any stride: the input's)"""
+    lib = _lib.load()
+    B, name = x.shape[0], f"moma_{entry}_bwd"
+    g = g.to(torch.float32).contiguous()              # the upstream gradient stays on the device (a GradScaler factor rides in it)
+    with _timed(name):
+        dF = torch.empty_strided(shape, strides, device=x.device, dtype=x.dtype)
+        check(getattr(lib, name)(_ptr(x), _ptr(M), _ptr(g), _ptr(dF), B, x.numel() // B, _DT_CODES[x.dtype], _stream()), name)
+    return dF
+
+
+# ------------------------------------------------------------------------------------------------
+# Relational Knowledge Distillation: pairwise distances and angles of a batch   (distiller_zoo/RKD.py, helper/loops_moma.py:155-158)
+# ------------------------------------------------------------------------------------------------
 
 
 class _RKDLoss(torch.autograd.Function):
@@ -1469,7 +1504,7 @@ class _RKDLoss(torch.autograd.Function):
     def forward(ctx, f_s, f_t, w_d, w_a):
         lib = _lib.load()
         shape = f_s.shape
-        x, y = _rkd_side(f_s, "f_s"), _rkd_side(f_t, "f_t")
+        x, y = _rel_side("rkd_loss", f_s, "f_s"), _rel_side("rkd_loss", f_t, "f_t")
         B, dev = x.shape[0], x.device
         with _timed("moma_rkd_fwd"):
             n = lib.moma_rkd_workspace_bytes(B)
@@ -1493,16 +1528,8 @@ class _RKDLoss(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         x, Q = ctx.saved_tensors
-        B, D = x.shape
-        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
-        with _timed("moma_rkd_bwd"):
-            dF = torch.empty(ctx.shape, device=x.device, dtype=x.dtype)          # (contiguous, as the input the kernels saw)
-            if dF.stride() != ctx.strides:                                       # (extents of 1 may carry any stride: the input's)
-                dF = dF.as_strided(ctx.shape, ctx.strides)
-            check(lib.moma_rkd_bwd(_ptr(x), _ptr(Q), _ptr(g), _ptr(dF), B, D, _DT_CODES[x.dtype], _stream()), "moma_rkd_bwd")
-        return dF, None, None, None
+        return _rel_backward("rkd", x, Q, g, ctx.shape, ctx.strides), None, None, None
 
 
 def rkd_loss(f_s, f_t, w_d=25.0, w_a=50.0) -> torch.Tensor:
@@ -1510,16 +1537,8 @@ def rkd_loss(f_s, f_t, w_d=25.0, w_a=50.0) -> torch.Tensor:
     or bfloat16, contiguous, independently per side; 2 <= B <= 1024) -> scalar float32:
     w_d * smooth_l1 of the mean-normalised pairwise distances + w_a * smooth_l1 of the angles at every anchor, both from the B x B
     matrices of squared distances in double (no [B, B, D] temporary).  The gradient flows to f_s only."""
-    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
-        _dev(t, nm, dtype=None, contiguous=False)
-        if t.dim() < 2:
-            raise ValueError(f"rkd_loss: {nm} must be [B, D] or [B, C, 1, 1], got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"rkd_loss: {nm} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
-    if f_t.requires_grad and torch.is_grad_enabled():
-        raise ValueError("rkd_loss: the kernels give no gradient to f_t (detach it, or use distiller_zoo.RKDLoss.composite)")
-    if f_s.shape[0] != f_t.shape[0]:
-        raise ValueError(f"rkd_loss: batch sizes {f_s.shape[0]} and {f_t.shape[0]} differ")
+    _rel_contiguous_sides("rkd_loss", f_s, f_t)
+    _rel_pair_guards("rkd_loss", "RKDLoss", f_s, f_t)
     if f_s.shape[0] < 2:
         raise ValueError("rkd_loss: relations need at least two rows, got B = 1")
     return _RKDLoss.apply(f_s, f_t, float(w_d), float(w_a))
@@ -1581,17 +1600,8 @@ class _SPLoss(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         f_s, M = ctx.saved_tensors
-        B = f_s.shape[0]
-        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
-        with _timed("moma_sp_bwd"):
-            dF = torch.empty_like(f_s)                # (same dtype, same strides: the storage order the kernels read)
-            if dF.stride() != f_s.stride():           # (extents of 1 may carry any stride: the input's)
-                dF = dF.as_strided(f_s.shape, f_s.stride())
-            check(lib.moma_sp_bwd(_ptr(f_s), _ptr(M), _ptr(g), _ptr(dF), B, f_s.numel() // B, _DT_CODES[f_s.dtype], _stream()),
-                  "moma_sp_bwd")
-        return dF, None
+        return _rel_backward("sp", f_s, M, g, f_s.shape, f_s.stride()), None
 
 
 def sp_loss(f_s, f_t) -> torch.Tensor:
@@ -1601,10 +1611,7 @@ def sp_loss(f_s, f_t) -> torch.Tensor:
     storage order (the Gram matrix does not depend on the order of the columns); the gradient flows to f_s only, in f_s's strides."""
     for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
         _sp_side(t, nm)
-    if f_t.requires_grad and torch.is_grad_enabled():
-        raise ValueError("sp_loss: the kernels give no gradient to f_t (detach it, or use distiller_zoo.Similarity.composite)")
-    if f_s.shape[0] != f_t.shape[0]:
-        raise ValueError(f"sp_loss: batch sizes {f_s.shape[0]} and {f_t.shape[0]} differ")
+    _rel_pair_guards("sp_loss", "Similarity", f_s, f_t)
     if f_s.shape[0] > _lib.SP_MAX_B:
         raise ValueError(f"sp_loss: the kernels take 1 .. {_lib.SP_MAX_B} rows, got {f_s.shape[0]}")
     return _SPLoss.apply(f_s, f_t)
@@ -1613,14 +1620,6 @@ def sp_loss(f_s, f_t) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 # Probabilistic Knowledge Transfer: cosine Gram of a batch as row distributions, their KL   (distiller_zoo/PKT.py, helper/loops_moma.py:159-162)
 # ------------------------------------------------------------------------------------------------
-def _pkt_side(f, name):
-    """-> [B, D] view of a contiguous [B, D] or [B, C, 1, 1] (any [B, ...]) float32 / bfloat16 device tensor"""
-    _dev(f, name, dtype=None, contiguous=False)
-    if f.dim() < 2 or f.dtype not in _DT_CODES:
-        raise TypeError(f"pkt_loss: {name} must be a float32 / bfloat16 tensor [B, ...], got {tuple(f.shape)} {f.dtype}")
-    return f.contiguous().view(f.shape[0], -1)
-
-
 class _PKTLoss(torch.autograd.Function):
     """pkt_gram_pair (both sides, one launch) -> pkt_terms (M with dF_s = g M f_s, loss; two launches) in the forward; pkt_bwd in the
     backward: one."""
@@ -1629,7 +1628,7 @@ class _PKTLoss(torch.autograd.Function):
     def forward(ctx, f_s, f_t):
         lib = _lib.load()
         shape = f_s.shape
-        x, y = _pkt_side(f_s, "f_s"), _pkt_side(f_t, "f_t")
+        x, y = _rel_side("pkt_loss", f_s, "f_s"), _rel_side("pkt_loss", f_t, "f_t")
         B, dev = x.shape[0], x.device
         with _timed("moma_pkt_fwd"):
             n = lib.moma_pkt_workspace_bytes(B)
@@ -1651,16 +1650,8 @@ class _PKTLoss(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         x, M = ctx.saved_tensors
-        B, D = x.shape
-        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
-        with _timed("moma_pkt_bwd"):
-            dF = torch.empty(ctx.shape, device=x.device, dtype=x.dtype)          # (contiguous, as the input the kernels saw)
-            if dF.stride() != ctx.strides:                                       # (extents of 1 may carry any stride: the input's)
-                dF = dF.as_strided(ctx.shape, ctx.strides)
-            check(lib.moma_pkt_bwd(_ptr(x), _ptr(M), _ptr(g), _ptr(dF), B, D, _DT_CODES[x.dtype], _stream()), "moma_pkt_bwd")
-        return dF, None
+        return _rel_backward("pkt", x, M, g, ctx.shape, ctx.strides), None
 
 
 def pkt_loss(f_s, f_t) -> torch.Tensor:
@@ -1669,16 +1660,8 @@ def pkt_loss(f_s, f_t) -> torch.Tensor:
     mean_ij T_ij log((T_ij + 1e-7) / (P_ij + 1e-7)), P and T the row-normalised (cosine + 1) / 2 matrices of the student's and the
     teacher's batch, from the raw B x B Gram matrices in double (no normalised copy of either side).  The gradient flows to f_s only;
     an all-zero student row gets a finite gradient (the reference's autograd: NaN)."""
-    for t, nm in ((f_s, "f_s"), (f_t, "f_t")):
-        _dev(t, nm, dtype=None, contiguous=False)
-        if t.dim() < 2:
-            raise ValueError(f"pkt_loss: {nm} must be [B, D] or [B, C, 1, 1], got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"pkt_loss: {nm} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
-    if f_t.requires_grad and torch.is_grad_enabled():
-        raise ValueError("pkt_loss: the kernels give no gradient to f_t (detach it, or use distiller_zoo.PKT.composite)")
-    if f_s.shape[0] != f_t.shape[0]:
-        raise ValueError(f"pkt_loss: batch sizes {f_s.shape[0]} and {f_t.shape[0]} differ")
+    _rel_contiguous_sides("pkt_loss", f_s, f_t)
+    _rel_pair_guards("pkt_loss", "PKT", f_s, f_t)
     if f_s.shape[0] > _lib.PKT_MAX_B:
         raise ValueError(f"pkt_loss: the kernels take 1 .. {_lib.PKT_MAX_B} rows, got {f_s.shape[0]}")
     return _PKTLoss.apply(f_s, f_t)
