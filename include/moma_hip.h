@@ -582,6 +582,18 @@ size_t moma_pwconv_workspace_bytes(int N, int Cin, int Cout, int HW);
 int moma_pwconv_bwd_weight(const void* x, const void* dy, void* dw, void* workspace, size_t workspace_bytes, int N, int Cin,
                            int Cout, int HW, int dtype, moma_stream_t stream);
 
+/*     Forward and input gradient of the same convolution on one streaming bf16 MFMA kernel (csrc/pwstream.hip): x is read once
+ *     in 16-byte rows as it lies in NCHW, transposed on the way out of LDS, and y is written in 16-byte pieces of 8 pixels.
+ *       moma_pwconv_fwd       y [N, Cout, HW] :  y[n, co, p]  = sum_ci w[co, ci] * x[n, ci, p]       (no bias)
+ *       moma_pwconv_bwd_data  dx [N, Cin, HW] :  dx[n, ci, p] = sum_co w[co, ci] * dy[n, co, p]
+ *     w [Cout, Cin] in both (the input gradient reads it transposed in place).  All operands dense, MOMA_DT_BF16, aligned to
+ *     2 bytes (16- / 8-byte accesses where HW and the addresses allow, element accesses otherwise: any N, Cin, Cout, HW >= 1 is
+ *     computed).  fp32 accumulation, one rounding to bf16.  No workspace, no atomics, no host synchronisation: bitwise
+ *     reproducible, safe under graph capture.  MOMA_DT_F32 is answered with MOMA_E_DTYPE; a refused call writes nothing. */
+int moma_pwconv_fwd(const void* x, const void* w, void* y, int N, int Cin, int Cout, int HW, int dtype, moma_stream_t stream);
+int moma_pwconv_bwd_data(const void* dy, const void* w, void* dx, int N, int Cin, int Cout, int HW, int dtype,
+                         moma_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * SE  squeeze-excite helpers on NCHW activations (models/efficientnet_pytorch/model.py:104-110):
  *     moma_plane_mean     mean[n,c] = mean_hw x[n,c,:,:]                       (F.adaptive_avg_pool2d(x, 1))

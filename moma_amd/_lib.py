@@ -90,6 +90,8 @@ SIGNATURES = {
     "moma_dwconv_bwd_weight_pre": (_i, [_p, _p, _p, _p, _z] + [_i] * 11 + [_p, _i, _p]),
     "moma_pwconv_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "moma_pwconv_bwd_weight": (_i, [_p, _p, _p, _p, _z] + [_i] * 5 + [_p]),
+    "moma_pwconv_fwd": (_i, [_p, _p, _p] + [_i] * 5 + [_p]),
+    "moma_pwconv_bwd_data": (_i, [_p, _p, _p] + [_i] * 5 + [_p]),
     "moma_plane_mean": (_i, [_p, _p, _i, _i, _i, _p]),
     "moma_se_gate_fwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "moma_se_gate_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),

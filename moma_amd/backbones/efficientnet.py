@@ -36,9 +36,16 @@ _SE_MODE = os.environ.get("MOMA_SE", "hip")
 _BNDW_FUSE = os.environ.get("MOMA_BNDW", "1")
 #   pointwise (1 x 1) convolutions: MOMA_PW=hip (default) = where the bf16 weight cache is live, the weight gradient runs on the
 #                           library's split-K MFMA kernel (pwconv.hip: one read of x and dy as they lie in NCHW, bitwise
-#                           reproducible); forward and input gradient stay MIOpen's strided GEMMs.  "miopen" = MIOpen in all
-#                           three directions (its weight-gradient solver transposes both operands into an NHWC workspace).
+#                           reproducible); forward and input gradient: MOMA_PWFWD below.  "miopen" = MIOpen in all three
+#                           directions (its weight-gradient solver transposes both operands into an NHWC workspace).
 _PW_MODE = os.environ.get("MOMA_PW", "hip")
+#   their forward and input gradient: MOMA_PWFWD=1 (default) = under MOMA_PW=hip the bias-free pointwise convolutions on spatial
+#                           planes (expand / project / head; not the squeeze-excite pair) run forward -- recorded or not: the
+#                           teacher's and the key passes too -- and input gradient on the library's streaming MFMA kernel
+#                           (pwstream.hip: x read once as it lies in NCHW, transposed on the way out of LDS) for the shape
+#                           classes of ops.pwconv_fwd_native (HW a multiple of 4, more than 16 output channels; any
+#                           batch), with or without the bf16 weight cache; 0 = MIOpen's strided GEMMs as before.
+_PW_FWD = os.environ.get("MOMA_PWFWD", "1")
 #   _bn1 + SiLU -> SE gate : MOMA_SEFUSE=1 (default) = where MOMA_BN and MOMA_SE both take their hip paths, BN1 + SiLU is applied inside
 #                           the gate, forward and backward (ops.bn_act_mean / ops.bn_act_gate, bnse.hip): the activation between
 #                           the two is neither written, read back nor kept for the backward -- one pass over the depthwise
@@ -142,6 +149,14 @@ class SamePadConv2d(nn.Conv2d):
         """Whether a call on an input of this device kind and dtype goes through ops.pwconv (asked without a device)."""
         return _PW_MODE == "hip" and self._wc_live and is_cuda and dtype == torch.bfloat16 and self._is_pointwise()
 
+    def _takes_pwfwd(self, is_cuda, dtype, n, hw):
+        """Whether the forward (and input gradient) of a call on [n, Cin, *] planes of hw pixels runs on the streaming kernel."""
+        if not (_PW_MODE == "hip" and _PW_FWD == "1" and is_cuda and dtype == torch.bfloat16 and self._is_pointwise()
+                and self.bias is None):                 # (with or without a live weight cache: the cache must stay transparent)
+            return False
+        from .. import ops
+        return ops.pwconv_fwd_native(n, self.in_channels, self.out_channels, hw)
+
     def forward(self, x):
         ih, iw = x.shape[-2:]
         kh, kw = self.kernel_size
@@ -168,9 +183,24 @@ class SamePadConv2d(nn.Conv2d):
                 torch.get_autocast_dtype("cuda") == torch.bfloat16:
             x = x.to(torch.bfloat16)
         w, b = self._params(x)
-        if self._takes_pwconv(x.is_cuda, x.dtype) and torch.is_grad_enabled() and w.requires_grad:
+        wgrad = self._takes_pwconv(x.is_cuda, x.dtype)
+        native_fwd = False
+        if x.dim() == 4 and x.is_cuda and self.bias is None:
+            # the streaming forward does not depend on the weight cache: without it the input and the master weight are cast as
+            # autocast would cast them for F.conv2d
+            xb = x
+            if x.dtype != torch.bfloat16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
+                xb = x.to(torch.bfloat16)
+            if self._takes_pwfwd(xb.is_cuda, xb.dtype, xb.shape[0], ih * iw):
+                wb = w if w.dtype == torch.bfloat16 else (w.to(torch.bfloat16) if torch.is_autocast_enabled() else None)
+                if wb is not None:
+                    x, w, native_fwd = xb, wb, True
+        if wgrad or native_fwd:
             from .. import ops
-            return ops.pwconv(x, w, b)
+            if torch.is_grad_enabled() and w.requires_grad:
+                return ops.pwconv(x, w, b, native_fwd, wgrad)
+            if native_fwd and not (torch.is_grad_enabled() and x.requires_grad):
+                return ops.pwconv_fwd(x, w)
         return F.conv2d(x, w, b, self.stride, pad, self.dilation, self.groups)
 
 

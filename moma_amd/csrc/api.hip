@@ -655,6 +655,24 @@ int moma_pwconv_bwd_weight(const void* x, const void* dy, void* dw, void* worksp
     return hip_rc(launch_pw_bwd_weight(x, dy, dw, (float*)workspace, N, Cin, Cout, HW, (hipStream_t)stream));
 }
 
+static int pw_stream_call(const void* x, const void* w, void* y, int N, int Cin, int Cout, int HW, int dtype, int transposed,
+                          moma_stream_t stream) {
+    if (!x || !w || !y) return MOMA_E_NULL;
+    if (pw_bad_shape(N, Cin, Cout, HW)) return MOMA_E_SHAPE;
+    if (dtype != MOMA_DT_BF16) return MOMA_E_DTYPE;          // (MOMA_DT_F32 included: the caller keeps its stock path for fp32)
+    if (misaligned(x, 2) || misaligned(w, 2) || misaligned(y, 2)) return MOMA_E_ALIGN;
+    return hip_rc(launch_pw_stream(x, w, y, N, Cin, Cout, HW, transposed, (hipStream_t)stream));
+}
+
+int moma_pwconv_fwd(const void* x, const void* w, void* y, int N, int Cin, int Cout, int HW, int dtype, moma_stream_t stream) {
+    return pw_stream_call(x, w, y, N, Cin, Cout, HW, dtype, 0, stream);
+}
+
+int moma_pwconv_bwd_data(const void* dy, const void* w, void* dx, int N, int Cin, int Cout, int HW, int dtype,
+                         moma_stream_t stream) {
+    return pw_stream_call(dy, w, dx, N, Cin, Cout, HW, dtype, 1, stream);
+}
+
 static int se_check(int NC, int HW, int dtype) {
     if (NC <= 0 || HW <= 0) return MOMA_E_SHAPE;
     if (dtype != MOMA_DT_F32 && dtype != MOMA_DT_BF16) return MOMA_E_DTYPE;

@@ -391,6 +391,9 @@ size_t pwconv_workspace_floats(int N, int Cin, int Cout, int HW);
 hipError_t launch_pw_bwd_weight(const void* x, const void* dy, void* dw, float* ws, int N, int Cin, int Cout, int HW,
                                 hipStream_t st);
 
+// ---- pwstream.hip (pointwise convolution, NCHW: forward and input gradient as one streaming bf16 MFMA product) ---------
+hipError_t launch_pw_stream(const void* x, const void* w, void* y, int N, int Cin, int Cout, int HW, int transposed, hipStream_t st);
+
 // ---- se.hip (squeeze-excite: per-plane mean, sigmoid gate) ----------------------------------------------
 hipError_t launch_plane_mean(const void* x, void* out, int NC, int HW, int dtype, hipStream_t st);
 hipError_t launch_se_gate_fwd(const void* x, const void* s, void* out, int NC, int HW, int dtype, hipStream_t st);

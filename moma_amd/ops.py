@@ -780,8 +780,8 @@ def dwconv(x, weight, stride: int, pad_top: int, pad_left: int, out_h: int, out_
 
 
 # ------------------------------------------------------------------------------------------------
-# Pointwise (1 x 1) convolution on NCHW activations: stock forward and input gradient, the weight gradient on the library's
-# split-K MFMA kernel (backbone helper, include/moma_hip.h "PW")
+# Pointwise (1 x 1) convolution on NCHW activations: the weight gradient on the library's split-K MFMA kernel, forward and
+# input gradient of the bias-free layers on its streaming MFMA kernel (backbone helper, include/moma_hip.h "PW")
 # ------------------------------------------------------------------------------------------------
 def pwconv_native(N: int, Cin: int, Cout: int, HW: int) -> bool:
     """Shape classes whose weight gradient the native kernel takes; the others keep MIOpen's solver.  By the layer table of
@@ -810,15 +810,63 @@ def pwconv_bwd_weight(x, dy):
     return dw
 
 
+def pwconv_fwd_native(N: int, Cin: int, Cout: int, HW: int) -> bool:
+    """Shape classes whose bias-free forward and input gradient (Cin and Cout as the layer has them: one table serves both) the
+    streaming kernel takes; the others keep MIOpen's GEMMs.  By the layer table of DESIGN.md 5a
+    (profiles/pwfwd_layer_microbench.txt, B = 256): planes whose rows allow 8- or 16-byte accesses (HW a multiple of 4: 112^2 ..
+    14^2) win 1.4 - 3.7 x forward (672 -> 112: 1.09 x) and 1.3 - 3.9 x backward (112 -> 672: at parity, 1.02 x); the 7 x 7 layers
+    (49-pixel rows: element accesses) lose up to 1.7 x and stay with MIOpen, as do the 1 x 1 planes of the squeeze-excite layers
+    (a bias, negligible bytes).  The batch does not enter: the class is the layer's, smaller batches were not timed.
+    Layers of at most 16 output channels (32 -> 16 on 112^2) stay although the kernel is 3 x faster there: MIOpen's solver for
+    them is the one whose results differ from the kernel's (every other routed layer agrees with MIOpen bit for bit on the
+    table's data), and with it replaced the seeded step's outputs moved by eight times their run-to-run difference."""
+    return HW > 1 and HW % 4 == 0 and Cout > 16
+
+
+def _pw_stream(entry, x, w, transposed):
+    lib = _lib.load()
+    _dev(x, "x", dtype=torch.bfloat16, contiguous=False)
+    _dev(w, "weight", dtype=torch.bfloat16, contiguous=False)
+    if x.dim() != 4 or w.dim() != 4 or w.shape[2:] != (1, 1):
+        raise ValueError(f"{entry}: x {tuple(x.shape)}, weight {tuple(w.shape)}")
+    x = x.contiguous()
+    w = w.contiguous()
+    N, _, H, W = x.shape
+    Cout, Cin = w.shape[:2]
+    if x.shape[1] != (Cout if transposed else Cin):
+        raise ValueError(f"{entry}: x {tuple(x.shape)}, weight {tuple(w.shape)}")
+    y = torch.empty(N, Cin if transposed else Cout, H, W, device=x.device, dtype=torch.bfloat16)
+    check(getattr(lib, entry)(_ptr(x), _ptr(w), _ptr(y), N, Cin, Cout, H * W, DT_BF16, _stream()), entry)
+    return y
+
+
+def pwconv_fwd(x, w):
+    """y [N, Cout, H, W] bf16 = conv2d(x, w) for w [Cout, Cin, 1, 1], no bias, on the streaming kernel (x, w bf16).  A dense NCHW
+    x is read where it lies; any other layout (channels-last, a strided view) is first copied dense, an activation-sized pass of
+    its own.  Bitwise reproducible; no host synchronisation (safe under graph capture)."""
+    return _pw_stream("moma_pwconv_fwd", x, w, False)
+
+
+def pwconv_bwd_data(dy, w):
+    """dx [N, Cin, H, W] bf16 of the same convolution from dy [N, Cout, H, W]; the weight is read transposed in place."""
+    return _pw_stream("moma_pwconv_bwd_data", dy, w, True)
+
+
 class _PWConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, native_fwd, native_wgrad):
         _dev(x, "x", dtype=torch.bfloat16, contiguous=False)
         _dev(w, "weight", dtype=torch.bfloat16, contiguous=False)
         if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[1] or w.shape[2:] != (1, 1):
             raise ValueError(f"pwconv: x {tuple(x.shape)}, weight {tuple(w.shape)}")
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
+        ctx.native_wgrad = bool(native_wgrad)
+        N, Cin, H, W = x.shape
+        # forward and input gradient on the streaming kernel: bias-free layers of the shape classes that win there
+        ctx.native_fwd = bool(native_fwd) and b is None and pwconv_fwd_native(N, Cin, w.shape[0], H * W)
+        if ctx.native_fwd:
+            return pwconv_fwd(x, w)
         return torch.nn.functional.conv2d(x, w, b)
 
     @staticmethod
@@ -826,23 +874,28 @@ class _PWConv(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                                                     [True, False, False])[0]
+            if ctx.native_fwd:
+                dx = pwconv_bwd_data(dy, w)
+            else:
+                dx = torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                                         [True, False, False])[0]
         if ctx.needs_input_grad[1]:
             N, Cin, H, W = x.shape
-            if pwconv_native(N, Cin, w.shape[0], H * W):
+            if ctx.native_wgrad and pwconv_native(N, Cin, w.shape[0], H * W):
                 dw = pwconv_bwd_weight(x, dy)
             else:
                 dw = torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
                                                          [False, True, False])[1]
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = dy.sum((0, 2, 3))
-        return dx, dw, db
+        return dx, dw, db, None, None
 
 
-def pwconv(x, w, b=None):
-    """conv2d with a [Cout, Cin, 1, 1] weight (stride 1, no padding) on bf16 NCHW activations."""
-    return _PWConv.apply(x, w, b)
+def pwconv(x, w, b=None, native_fwd=True, native_wgrad=True):
+    """conv2d with a [Cout, Cin, 1, 1] weight (stride 1, no padding) on bf16 NCHW activations.  With `native_wgrad` the weight
+    gradient runs on the split-K kernel (pwconv_native); without a bias and with `native_fwd`, forward and input gradient run on
+    the streaming kernel where pwconv_fwd_native holds.  Everything else is the stock path."""
+    return _PWConv.apply(x, w, b, native_fwd, native_wgrad)
 
 
 # ------------------------------------------------------------------------------------------------
