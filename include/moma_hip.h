@@ -302,6 +302,41 @@ int moma_nst_bwd(const void* f_s, const void* f_t, const void* workspace, size_t
                  int dtype_t, int layout_t, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * VID  Variational Information Distillation (`--distill vid`) on one pair of maps on a COMMON grid -- replaces the Gaussian negative
+ *      log-likelihood at the end of VIDLoss.forward (distiller_zoo/VID.py: softplus(log_scale) + eps -> 0.5 ((pred_mean - target)^2
+ *      / pred_var + log pred_var) -> mean) and its autograd backward to pred_mean and log_scale.  For mean (the regressor's output)
+ *      and target, both [B,C,H,W], P = H W, log_scale [C]:
+ *          var_c  = log(1 + exp(log_scale_c)) + eps                  (evaluated in double)
+ *          S_c    = sum_(b,p) (mean - target)[b,c,p]^2
+ *          loss   = 0.5 / C * sum_c ( S_c / (B P var_c) + log var_c )
+ *          d_mean = g_loss * (mean - target) / (var_c * B C P)
+ *          d_var_c       = 0.5 / C * ( 1 / var_c - S_c / (B P var_c^2) )
+ *          d_log_scale_c = d_var_c * exp(log_scale_c) / (1 + exp(log_scale_c))      (before g_loss: the caller multiplies)
+ *      mean, target, d_mean: MOMA_DT_F32 or MOMA_DT_BF16 and MOMA_LAYOUT_NCHW or MOMA_LAYOUT_NHWC, each chosen per side (d_mean as
+ *      mean), dense, aligned to their element size -- 16-byte accesses where the address and the contiguous extent (P, or C) allow,
+ *      element accesses otherwise; a target in the other layout than mean is read element by element.  Everything else is fp32.
+ *      Differences and squares in fp32; a thread's fp32 sum is at most 16 squares long, everything across lanes, waves, workgroups
+ *      and partials is added in double, as is all [C] arithmetic.  No atomics: partial sums meet in a fixed order in a second
+ *      launch, results are bitwise reproducible.  The target gets no gradient.
+ *      DEVIATION: the softplus is evaluated in double in its overflow-free form, so var, loss and d_log_scale stay finite for any
+ *      finite log_scale; the reference's fp32 exp(log_scale) is inf for log_scale above about 88.
+ *
+ * workspace     moma_vid_workspace_bytes() = B ceil(P / MOMA_VID_CHUNK) C 8 bytes, 8-byte aligned: one double per image, chunk of
+ *               MOMA_VID_CHUNK pixels and channel, written by the streaming kernel and added in order by the finalize kernel.
+ * moma_vid_nll  one read of mean and of target -> sq [C] (S_c), var [C], g_log_scale [C], loss [1].  Two launches.
+ * moma_vid_bwd  d_mean from one read of mean, target and var [C]; g_loss is a DEVICE scalar (the upstream gradient of the loss,
+ *               e.g. a GradScaler factor): nothing is read back to the host.
+ *      Unknown dtype or layout: MOMA_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_VID_CHUNK = 1024 };
+size_t moma_vid_workspace_bytes(int B, int C, int P, int dtype_m, int layout_m, int dtype_t, int layout_t);
+int moma_vid_nll(const void* mean, const void* target, const float* log_scale, float eps, int B, int C, int P, int dtype_m,
+                 int layout_m, int dtype_t, int layout_t, void* workspace, size_t workspace_bytes, float* sq, float* var,
+                 float* g_log_scale, float* loss, moma_stream_t stream);
+int moma_vid_bwd(const void* mean, const void* target, const float* var, const float* g_loss, void* d_mean, int B, int C, int P,
+                 int dtype_m, int layout_m, int dtype_t, int layout_t, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * RKD  Relational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
  *      (distiller_zoo/RKD.py: pdist -> smooth L1 of the mean-normalised distances, and unsqueeze-difference -> F.normalize -> bmm ->
  *      smooth L1 of the angles) and its autograd backward to f_s, without any [B, B, D] temporary.  For f_s [B, Ds], f_t [B, Dt]

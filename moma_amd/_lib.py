@@ -15,6 +15,7 @@ PREC_F32, PREC_BF16 = 0, 1
 DT_F32, DT_BF16 = 0, 1
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 NST_MAX_C, NST_ROW_BLOCK = 256, 32
+VID_CHUNK = 1024
 RKD_MAX_B = 1024
 SP_MAX_B = 1024
 PKT_MAX_B = 1024
@@ -62,6 +63,9 @@ SIGNATURES = {
     "moma_nst_workspace_bytes": (_z, [_i] * 3),
     "moma_nst_gram": (_i, [_p, _p] + [_i] * 8 + [_p, _z, _p, _p, _p, _p, _p, _p]),
     "moma_nst_bwd": (_i, [_p, _p, _p, _z, _p, _p, _p, _p] + [_i] * 8 + [_p]),
+    "moma_vid_workspace_bytes": (_z, [_i] * 7),
+    "moma_vid_nll": (_i, [_p, _p, _p, _f] + [_i] * 7 + [_p, _z, _p, _p, _p, _p, _p]),
+    "moma_vid_bwd": (_i, [_p, _p, _p, _p, _p] + [_i] * 7 + [_p]),
     "moma_rkd_workspace_bytes": (_z, [_i]),
     "moma_rkd_dist": (_i, [_p, _i, _i, _i, _p, _p]),
     "moma_rkd_terms": (_i, [_p, _p, _i, _f, _f, _p, _z, _p, _p, _p, _p]),

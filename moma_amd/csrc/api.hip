@@ -861,6 +861,48 @@ int moma_nst_bwd(const void* f_s, const void* f_t, const void* workspace, size_t
                                  layout_t, (hipStream_t)stream));
 }
 
+// ---- Variational Information Distillation ---------------------------------------------------------------------------------------
+static int vid_check(int B, int C, int P, int dtype_m, int layout_m, int dtype_t, int layout_t) {
+    if (B <= 0 || C <= 0 || P <= 0) return MOMA_E_SHAPE;
+    if (bad_dt(dtype_m) || bad_dt(dtype_t)) return MOMA_E_UNSUPPORTED;
+    if ((layout_m != MOMA_LAYOUT_NCHW && layout_m != MOMA_LAYOUT_NHWC) || (layout_t != MOMA_LAYOUT_NCHW && layout_t != MOMA_LAYOUT_NHWC))
+        return MOMA_E_UNSUPPORTED;
+    if (P > INT32_MAX / 2 || C > INT32_MAX / 2) return MOMA_E_UNSUPPORTED;      // (pixel and channel indices of one image are ints)
+    return MOMA_OK;
+}
+
+size_t moma_vid_workspace_bytes(int B, int C, int P, int dtype_m, int layout_m, int dtype_t, int layout_t) {
+    if (vid_check(B, C, P, dtype_m, layout_m, dtype_t, layout_t) != MOMA_OK) return 0;
+    return vid_workspace_bytes(B, C, P);
+}
+
+int moma_vid_nll(const void* mean, const void* target, const float* log_scale, float eps, int B, int C, int P, int dtype_m,
+                 int layout_m, int dtype_t, int layout_t, void* workspace, size_t workspace_bytes, float* sq, float* var,
+                 float* g_log_scale, float* loss, moma_stream_t stream) {
+    if (!mean || !target || !log_scale || !workspace || !sq || !var || !g_log_scale || !loss) return MOMA_E_NULL;
+    const int rc = vid_check(B, C, P, dtype_m, layout_m, dtype_t, layout_t);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < vid_workspace_bytes(B, C, P)) return MOMA_E_WORKSPACE;
+    if (misaligned(mean, dtype_m == MOMA_DT_BF16 ? 2 : 4) || misaligned(target, dtype_t == MOMA_DT_BF16 ? 2 : 4) ||
+        misaligned(workspace, 8) || misaligned(log_scale, 4) || misaligned(sq, 4) || misaligned(var, 4) || misaligned(g_log_scale, 4) ||
+        misaligned(loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_vid_nll(mean, target, log_scale, eps, B, C, P, dtype_m, layout_m, dtype_t, layout_t, (double*)workspace, sq,
+                                 var, g_log_scale, loss, (hipStream_t)stream));
+}
+
+int moma_vid_bwd(const void* mean, const void* target, const float* var, const float* g_loss, void* d_mean, int B, int C, int P,
+                 int dtype_m, int layout_m, int dtype_t, int layout_t, moma_stream_t stream) {
+    if (!mean || !target || !var || !g_loss || !d_mean) return MOMA_E_NULL;
+    const int rc = vid_check(B, C, P, dtype_m, layout_m, dtype_t, layout_t);
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype_m == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(mean, eb) || misaligned(d_mean, eb) || misaligned(target, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(var, 4) ||
+        misaligned(g_loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_vid_bwd(mean, target, var, g_loss, d_mean, B, C, P, dtype_m, layout_m, dtype_t, layout_t, (hipStream_t)stream));
+}
+
 // ---- The losses on a B x B batch relation (rkd, sp, pkt): the guards they share ---------------------------------------------------
 // f [B, D] of `dtype` with lo <= B <= hi
 static int rel_check(int B, long long D, int dtype, int lo, int hi) {

@@ -282,6 +282,15 @@ hipError_t launch_nst_gram(const void* fs, const void* ft, int B, int Cs, int Ct
 hipError_t launch_nst_bwd(const void* fs, const void* ft, const float* G, const float* norms, const float* rows, const float* g_loss,
                           void* dF, int B, int Cs, int Ct, int P, int dt_s, int lay_s, int dt_t, int lay_t, hipStream_t st);
 
+// ---- vid.hip (Variational Information Distillation: the per-channel Gaussian NLL of a regressor's output, its gradients) --------
+long long vid_partial_rows(int B, int P);
+size_t vid_workspace_bytes(int B, int C, int P);
+hipError_t launch_vid_nll(const void* mean, const void* target, const float* log_scale, float eps, int B, int C, int P, int dt_m,
+                          int lay_m, int dt_t, int lay_t, double* partials, float* sq, float* var, float* g_log_scale, float* loss,
+                          hipStream_t st);
+hipError_t launch_vid_bwd(const void* mean, const void* target, const float* var, const float* g_loss, void* d_mean, int B, int C,
+                          int P, int dt_m, int lay_m, int dt_t, int lay_t, hipStream_t st);
+
 // ---- rkd.hip (Relational Knowledge Distillation: pairwise squared distances, the distance and angle terms, the student's gradient) --
 size_t rkd_workspace_bytes(int B);
 hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st);

@@ -4,5 +4,6 @@ from .NST import NSTLoss
 from .PKT import PKT
 from .RKD import RKDLoss
 from .SP import Similarity
+from .VID import VIDLoss
 
-__all__ = ["Attention", "DistillKL", "NSTLoss", "PKT", "RKDLoss", "Similarity"]
+__all__ = ["Attention", "DistillKL", "NSTLoss", "PKT", "RKDLoss", "Similarity", "VIDLoss"]

@@ -39,6 +39,13 @@ order).  Nothing to train besides the student, no memory; the step is eager.
 feature, through the same teacher branch as `rkd` (feat_t[-1] rides detached in the key slot, in the dtype autocast left it:
 csrc/pkt.hip reads fp32 / bf16 per side and does its arithmetic in double).  Nothing to train besides the student, no memory; the
 step is eager.
+
+`--distill vid` (reference :145-149): the KD term is sum(c(f_s, f_t) for f_s, f_t, c in zip(feat_s[1:-1], feat_t[1:-1], criterion_kd))
+-- Variational Information Distillation, one VIDLoss per intermediate pair, through the same teacher branch as `attention` (one eager
+no-grad forward with every feature map).  The criterion is a ModuleList with trained state (a 1 x 1 regressor and a per-channel
+log_scale per pair): it sits in the optimizer, its regressors run under the step's autocast, its Gaussian likelihood on csrc/vid.hip
+(fp32 / bf16, NCHW / channels_last per side), and its gradients are synchronised across ranks with those of the other trainable
+criteria.  No memory; the step is eager.
 """
 from __future__ import print_function
 
@@ -129,10 +136,10 @@ class MomaStep:
         """teacher forward #1 (:270-272), then the moma branch's no-grad part (:309-320, :327-329)."""
         opt, trainer, criterion_kd, model_t = self.opt, self.trainer, self.criterion_kd, self.model_t
         with self.autocast(), torch.no_grad():
-            if opt.distill in ("attention", "nst", "similarity"):    # (:270-272, :287-292 / :150-154 / :140-144) every feature map, as autocast left it: an eager forward
+            if opt.distill in ("attention", "nst", "similarity", "vid"):    # (:270-272, :287-292 / :150-154 / :140-144 / :145-149) every feature map, as autocast left it: an eager forward
                 ft, lt = teacher(images, is_feat=True, full_feats=True) if isinstance(teacher, GraphedInference) \
                     else teacher(images, is_feat=True)
-                ft = ft[1:-1] if opt.distill == "attention" else ft[1:-2] if opt.distill == "nst" else [ft[-2]]
+                ft = ft[1:-1] if opt.distill in ("attention", "vid") else ft[1:-2] if opt.distill == "nst" else [ft[-2]]
                 return lt.float(), [f.detach() for f in ft], None                # g_t rides in the key slot
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
@@ -192,6 +199,8 @@ class MomaStep:
             out["g_s"] = list(feat_s[1:-1])                                               # (:289)
         if opt.distill == "nst":
             out["g_s"] = list(feat_s[1:-2])                                               # (:151)
+        if opt.distill == "vid":
+            out["g_s"] = list(feat_s[1:-1])                                               # (:146)
         if opt.distill == "similarity":
             out["g_s"] = [feat_s[-2]]                                                     # (:141)
         if opt.distill == "rkd":
@@ -259,6 +268,9 @@ class MomaStep:
                 return criterion_kd(fw["f_s"], fw["k"], fw["index"], fw["contrast_idx"]).float()
         if opt.distill in ("attention", "nst", "similarity"):                             # (:287-292 / :150-154 / :140-144) g_t rides in fw["k"]
             return sum(criterion_kd(fw["g_s"], fw["k"])).float()
+        if opt.distill == "vid":                                                          # (:145-149) one criterion per pair; g_t rides in fw["k"]
+            with self.autocast():                                                         # (the regressors are convolutions)
+                return sum(c(f_s, f_t) for f_s, f_t, c in zip(fw["g_s"], fw["k"], criterion_kd)).float()
         if opt.distill == "rkd":                                                          # (:155-158) f_t rides in fw["k"]
             return criterion_kd(fw["f_s"], fw["k"]).float()
         if opt.distill == "pkt":                                                          # (:159-162) likewise
@@ -330,14 +342,14 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             if torch.cuda.is_available() else torch.device("cpu")
     step = MomaStep(module_list, criterion_list, trainer, contrast, optimizer, opt, dev)
     single_rank = bool(getattr(trainer, "grad_sync_single_rank", False))
-    sync_criterion = opt.distill in ("moma", "crd") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
+    sync_criterion = opt.distill in ("moma", "crd", "vid") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
     flat_dp = isinstance(model_s, FlatDataParallel)
     flat_params = None
     if flat_dp:
         # learning/ddp.py: ONE flat all-reduce per step behind the backward -- the student's gradients and those of the trainable
         # criterion modules (atts_q / embed_s: not under any wrapper, un-synchronised in the reference)
         flat_params = model_s.grad_params()
-        if opt.distill in ("moma", "crd"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank)
+        if opt.distill in ("moma", "crd", "vid"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
             flat_params = flat_params + [p for p in criterion_kd.parameters() if p.requires_grad]
     elif sync_criterion:
         # stock DDP on the student: one flat all-reduce per step for the trainable criterion modules, launched from autograd

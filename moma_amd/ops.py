@@ -1505,6 +1505,79 @@ def nst_loss(f_s, f_t) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# Variational Information Distillation: per-channel Gaussian NLL of a regressor's output   (distiller_zoo/VID.py, helper/loops_moma.py:145-149)
+# ------------------------------------------------------------------------------------------------
+def _vid_side(f, name):
+    """-> layout code of a dense [B,C,H,W] float32 / bfloat16 device tensor (contiguous or channels_last, taken as it lies)"""
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() != 4 or f.dtype not in _DT_CODES:
+        raise TypeError(f"vid_nll: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+    if f.is_contiguous():
+        return _lib.LAYOUT_NCHW
+    if f.is_contiguous(memory_format=torch.channels_last):
+        return _lib.LAYOUT_NHWC
+    raise ValueError(f"vid_nll: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is neither contiguous nor channels_last "
+                     "(use distiller_zoo.VIDLoss.composite)")
+
+
+class _VIDNLL(torch.autograd.Function):
+    """vid_nll (S, var, d loss / d log_scale, loss) in the forward; vid_bwd (d_mean from the two maps and var) in the backward."""
+
+    @staticmethod
+    def forward(ctx, mean, target, log_scale, eps):
+        lib = _lib.load()
+        lay_m, lay_t = _vid_side(mean, "mean"), _vid_side(target, "target")
+        _dev(log_scale, "log_scale", torch.float32)
+        B, Cc, H, W = mean.shape
+        if tuple(target.shape) != (B, Cc, H, W) or tuple(log_scale.shape) != (Cc,):
+            raise ValueError(f"vid_nll: mean {tuple(mean.shape)}, target {tuple(target.shape)} and log_scale {tuple(log_scale.shape)} "
+                             "do not agree")
+        dev, P = mean.device, H * W
+        codes = (_DT_CODES[mean.dtype], lay_m, _DT_CODES[target.dtype], lay_t)
+        with _timed("moma_vid_fwd"):
+            n = lib.moma_vid_workspace_bytes(B, Cc, P, *codes)
+            if n == 0:
+                raise ValueError(f"vid_nll: no workspace for mean {tuple(mean.shape)}")
+            ws = torch.empty(n // 8, device=dev, dtype=torch.float64)
+            sq, var, g_ls = (torch.empty(Cc, device=dev, dtype=torch.float32) for _ in range(3))
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            check(lib.moma_vid_nll(_ptr(mean), _ptr(target), _ptr(log_scale), float(eps), B, Cc, P, *codes, _ptr(ws), n, _ptr(sq),
+                                   _ptr(var), _ptr(g_ls), _ptr(loss), _stream()), "moma_vid_nll")
+        ctx.save_for_backward(mean, target, var, g_ls)
+        ctx.codes = codes
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        mean, target, var, g_ls = ctx.saved_tensors
+        B, Cc, H, W = mean.shape
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        d_mean = None
+        if ctx.needs_input_grad[0]:
+            with _timed("moma_vid_bwd"):
+                d_mean = torch.empty_like(mean)       # (same dtype, same strides: NCHW or channels_last)
+                check(lib.moma_vid_bwd(_ptr(mean), _ptr(target), _ptr(var), _ptr(g), _ptr(d_mean), B, Cc, H * W, *ctx.codes,
+                                       _stream()), "moma_vid_bwd")
+        return d_mean, None, (g * g_ls if ctx.needs_input_grad[2] else None), None
+
+
+def vid_nll(mean, target, log_scale, eps=1e-5) -> torch.Tensor:
+    """Gaussian negative log-likelihood of Variational Information Distillation: mean (the regressor's output) and target, both
+    [B,C,H,W] (float32 or bfloat16, contiguous or channels_last, independently per side), log_scale [C] float32 -> scalar float32:
+    0.5 mean_(b,c,p) ((mean - target)^2 / var_c + log var_c), var_c = softplus(log_scale_c) + eps.  Gradients flow to mean (in its
+    dtype and strides) and to log_scale; the target gets none."""
+    for t, nm in ((mean, "mean"), (target, "target")):
+        _dev(t, nm, dtype=None, contiguous=False)
+        if t.dim() != 4:
+            raise ValueError(f"vid_nll: {nm} must be [B,C,H,W], got {tuple(t.shape)}")
+    if target.requires_grad and torch.is_grad_enabled():
+        raise ValueError("vid_nll: the kernels give no gradient to the target (detach it, or use distiller_zoo.VIDLoss.composite)")
+    return _VIDNLL.apply(mean, target, log_scale, float(eps))
+
+
+# ------------------------------------------------------------------------------------------------
 # What the losses on a B x B batch relation (rkd, sp, pkt: below) share: guards, the [B, D] view, the backward call
 # ------------------------------------------------------------------------------------------------
 def _rel_side(op, f, name):

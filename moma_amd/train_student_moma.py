@@ -12,7 +12,10 @@ and launch lines carry over.  What differs:
     (Similarity-Preserving distillation on the head map feat[-2]: distiller_zoo/SP.py on the batch-Gram kernels of csrc/sp.hip; the
     reference ships no launch line for it, the published one of RepDistiller is `--distill similarity -a 0 -b 3000`), `pkt` (Probabilistic
     Knowledge Transfer on the last feature: distiller_zoo/PKT.py on the cosine-Gram and KL kernels of csrc/pkt.hip; the reference
-    ships no launch line for it either, the published one of RepDistiller is `--distill pkt -a 0 -b 30000`) and `crd` (Contrastive
+    ships no launch line for it either, the published one of RepDistiller is `--distill pkt -a 0 -b 30000`), `vid` (Variational
+    Information Distillation over the intermediate feature maps: one distiller_zoo/VID.py per pair, its 1 x 1 regressor and per-channel
+    log_scale trained with the student, checkpointed and resumed with it, the Gaussian likelihood on the kernels of csrc/vid.hip; the
+    reference ships no launch line for it either, the published one of RepDistiller is `--distill vid -a 0 -b 1`) and `crd` (Contrastive
     Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
     `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
     built -- the other comparison criteria are out of scope (SURVEY section 2);
@@ -49,7 +52,7 @@ from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
-from .distiller_zoo import PKT, Attention, DistillKL, NSTLoss, RKDLoss, Similarity
+from .distiller_zoo import PKT, Attention, DistillKL, NSTLoss, RKDLoss, Similarity, VIDLoss
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
 from .learning.contrast_trainer import ContrastTrainer
@@ -241,6 +244,13 @@ def build_training(opt, device):
         criterion_kd = Similarity()                               # reference train_student_moma.py:295-296: likewise
     elif opt.distill == "pkt":
         criterion_kd = PKT()                                      # reference train_student_comparison.py:384-385: likewise
+    elif opt.distill == "vid":
+        # reference train_student_comparison.py:304-311: one VIDLoss per intermediate pair, built in order (the regressors' weights
+        # are drawn here); its regressors and log_scale train, so the list joins the trainable list and reaches the optimizer
+        s_n = [f.shape[1] for f in feat_s[1:-1]]
+        t_n = [f.shape[1] for f in feat_t[1:-1]]
+        criterion_kd = nn.ModuleList([VIDLoss(s, t, t) for s, t in zip(s_n, t_n)])
+        trainable_list.append(criterion_kd)
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
@@ -421,7 +431,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         print("==> training...")
         t1 = time.time()
         train_acc, train_loss = train_distill_moma(epoch, train_loader, module_list, criterion_list,
-                                                   trainer if opt.distill in ("moma", "crd") else None, contrast, optimizer, opt)
+                                                   trainer if opt.distill in ("moma", "crd", "vid") else None, contrast, optimizer, opt)
         if device.type == "cuda":
             torch.cuda.synchronize()
         t2 = time.time()
