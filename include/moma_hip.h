@@ -337,7 +337,50 @@ int moma_vid_bwd(const void* mean, const void* target, const float* var, const f
                  int dtype_m, int layout_m, int dtype_t, int layout_t, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * RKD  Relational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
+ * HINT FitNets hint (`--distill hint`) on one pair of maps on a COMMON grid -- replaces what follows the convolution in
+ *      ConvReg.forward (models/util.py: BatchNorm2d in training mode -> ReLU) together with HintLoss (distiller_zoo/FitNet.py:
+ *      MSELoss) and their autograd backward.  For x (the convolution's output) and t (the teacher's map), both [B,C,H,W], P = H W,
+ *      M = B P, N = B C P, gamma and beta [C]:
+ *          mean_c = sum x / M       var_c = sum x^2 / M - mean_c^2   (biased; sums and variance in double)
+ *          invstd_c = 1 / sqrt(var_c + eps)       xh = (x - mean_c) invstd_c   (centred and scaled in double, rounded to fp32)
+ *          y = max(0, gamma_c xh + beta_c)        loss = sum (y - t)^2 / N
+ *          g = (y - t) [y > 0]                    (strictly greater: ReLU's derivative at 0 is 0, as in torch)
+ *          A_c = sum_(b,p) g        B_c = sum_(b,p) g xh        k = 2 g_loss / N
+ *          d_beta_c = k A_c         d_gamma_c = k B_c           dx = k gamma_c invstd_c (g - A_c / M - xh B_c / M)
+ *          running_mean_c <- (1 - momentum) running_mean_c + momentum (mean_c + conv_bias_c)
+ *          running_var_c  <- (1 - momentum) running_var_c  + momentum var_c M / (M - 1)
+ *      x, t, dx: MOMA_DT_F32 or MOMA_DT_BF16, MOMA_LAYOUT_NCHW or MOMA_LAYOUT_NHWC, each chosen per side, dense, aligned to their
+ *      element size (16-byte accesses where the base address and the contiguous extent allow); dx has x's dtype and layout.
+ *      gamma, beta, conv_bias, the running statistics, d_gamma, d_beta, loss and g_loss are fp32; mean, invstd, sums (A [C] then
+ *      B [C]) and the workspace are double, 8-byte aligned.  The arithmetic on an element is fp32 behind the double centring,
+ *      every sum double; a bf16 dx is rounded from the fp32 value.  No atomics: bitwise reproducible.  t gets no gradient.
+ *      conv_bias (nullable) is the bias of the convolution in front, which the caller has NOT added to x: in training mode a
+ *      per-channel constant in front of a BatchNorm changes running_mean and nothing else, so it enters there only, and its
+ *      gradient is exactly 0 (the reference's autograd returns rounding noise there).
+ *
+ * workspace      moma_hint_workspace_bytes() = 3 ceil(B / BI) ceil(P / MOMA_HINT_CHUNK) C 8 bytes, BI = max(1, min(B,
+ *                MOMA_HINT_CHUNK / P)): one double per sum, group of BI images (planes shorter than a chunk share one), chunk of
+ *                MOMA_HINT_CHUNK pixels and channel, written by the streaming kernels and added in order by the finalize kernels.
+ * moma_hint_fwd  two reads of x, one of t -> mean [C], invstd [C], sums [2 C] (A, B), loss [1]; running_mean / running_var
+ *                (each nullable) updated in place.  Four launches.
+ * moma_hint_bwd  dx (nullable) from one read of x and t and the saved [C] vectors, with no reduction of its own; d_gamma, d_beta
+ *                (each nullable) from sums.  g_loss is a DEVICE scalar (the upstream gradient of the loss, e.g. a GradScaler
+ *                factor): nothing is read back to the host.
+ *      M < 2: MOMA_E_SHAPE, nothing is launched (torch refuses "more than 1 value per channel" likewise); unknown dtype or layout:
+ *      MOMA_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_HINT_CHUNK = 1024 };
+size_t moma_hint_workspace_bytes(int B, int C, int P, int dtype_x, int layout_x, int dtype_t, int layout_t);
+int moma_hint_fwd(const void* x, const void* t, const float* gamma, const float* beta, const float* conv_bias, float* running_mean,
+                  float* running_var, float momentum, float eps, int B, int C, int P, int dtype_x, int layout_x, int dtype_t,
+                  int layout_t, void* workspace, size_t workspace_bytes, double* mean, double* invstd, double* sums, float* loss,
+                  moma_stream_t stream);
+int moma_hint_bwd(const void* x, const void* t, const float* gamma, const float* beta, const double* mean, const double* invstd,
+                  const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta, int B, int C, int P, int dtype_x,
+                  int layout_x, int dtype_t, int layout_t, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * RKDRelational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
  *      (distiller_zoo/RKD.py: pdist -> smooth L1 of the mean-normalised distances, and unsqueeze-difference -> F.normalize -> bmm ->
  *      smooth L1 of the angles) and its autograd backward to f_s, without any [B, B, D] temporary.  For f_s [B, Ds], f_t [B, Dt]
  *      (each side's feat[-1] flattened), per side S_ij = sum_k (x_ik - x_jk)^2, summed from the differences in double: exactly 0

@@ -903,6 +903,53 @@ int moma_vid_bwd(const void* mean, const void* target, const float* var, const f
     return hip_rc(launch_vid_bwd(mean, target, var, g_loss, d_mean, B, C, P, dtype_m, layout_m, dtype_t, layout_t, (hipStream_t)stream));
 }
 
+// ---- FitNets hint -----------------------------------------------------------------------------------------------------------------
+static int hint_check(int B, int C, int P, int dtype_x, int layout_x, int dtype_t, int layout_t) {
+    if (B <= 0 || C <= 0 || P <= 0) return MOMA_E_SHAPE;
+    if ((long long)B * P < 2) return MOMA_E_SHAPE;                   // one value per channel has no variance
+    if (bad_dt(dtype_x) || bad_dt(dtype_t)) return MOMA_E_UNSUPPORTED;
+    if ((layout_x != MOMA_LAYOUT_NCHW && layout_x != MOMA_LAYOUT_NHWC) || (layout_t != MOMA_LAYOUT_NCHW && layout_t != MOMA_LAYOUT_NHWC))
+        return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_hint_workspace_bytes(int B, int C, int P, int dtype_x, int layout_x, int dtype_t, int layout_t) {
+    if (hint_check(B, C, P, dtype_x, layout_x, dtype_t, layout_t) != MOMA_OK) return 0;
+    return hint_workspace_bytes(B, C, P);
+}
+
+int moma_hint_fwd(const void* x, const void* t, const float* gamma, const float* beta, const float* conv_bias, float* running_mean,
+                  float* running_var, float momentum, float eps, int B, int C, int P, int dtype_x, int layout_x, int dtype_t,
+                  int layout_t, void* workspace, size_t workspace_bytes, double* mean, double* invstd, double* sums, float* loss,
+                  moma_stream_t stream) {
+    if (!x || !t || !gamma || !beta || !workspace || !mean || !invstd || !sums || !loss) return MOMA_E_NULL;
+    const int rc = hint_check(B, C, P, dtype_x, layout_x, dtype_t, layout_t);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < hint_workspace_bytes(B, C, P)) return MOMA_E_WORKSPACE;
+    if (misaligned(x, dtype_x == MOMA_DT_BF16 ? 2 : 4) || misaligned(t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(workspace, 8) ||
+        misaligned(sums, 8) || misaligned(gamma, 4) || misaligned(beta, 4) || misaligned(conv_bias, 4) || misaligned(running_mean, 4) ||
+        misaligned(running_var, 4) || misaligned(mean, 8) || misaligned(invstd, 8) || misaligned(loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_hint_fwd(x, t, gamma, beta, conv_bias, running_mean, running_var, momentum, eps, B, C, P, dtype_x, layout_x,
+                                  dtype_t, layout_t, (double*)workspace, mean, invstd, sums, loss, (hipStream_t)stream));
+}
+
+int moma_hint_bwd(const void* x, const void* t, const float* gamma, const float* beta, const double* mean, const double* invstd,
+                  const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta, int B, int C, int P, int dtype_x,
+                  int layout_x, int dtype_t, int layout_t, moma_stream_t stream) {
+    if (!x || !t || !gamma || !beta || !mean || !invstd || !sums || !g_loss) return MOMA_E_NULL;
+    if (!dx && !d_gamma && !d_beta) return MOMA_E_NULL;
+    const int rc = hint_check(B, C, P, dtype_x, layout_x, dtype_t, layout_t);
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype_x == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(x, eb) || misaligned(dx, eb) || misaligned(t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(sums, 8) ||
+        misaligned(gamma, 4) || misaligned(beta, 4) || misaligned(mean, 8) || misaligned(invstd, 8) || misaligned(g_loss, 4) ||
+        misaligned(d_gamma, 4) || misaligned(d_beta, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_hint_bwd(x, t, gamma, beta, mean, invstd, sums, g_loss, dx, d_gamma, d_beta, B, C, P, dtype_x, layout_x,
+                                  dtype_t, layout_t, (hipStream_t)stream));
+}
+
 // ---- The losses on a B x B batch relation (rkd, sp, pkt): the guards they share ---------------------------------------------------
 // f [B, D] of `dtype` with lo <= B <= hi
 static int rel_check(int B, long long D, int dtype, int lo, int hi) {

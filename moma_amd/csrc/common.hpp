@@ -291,6 +291,17 @@ hipError_t launch_vid_nll(const void* mean, const void* target, const float* log
 hipError_t launch_vid_bwd(const void* mean, const void* target, const float* var, const float* g_loss, void* d_mean, int B, int C,
                           int P, int dt_m, int lay_m, int dt_t, int lay_t, hipStream_t st);
 
+// ---- hint.hip (FitNets hint: training-mode BatchNorm, ReLU and the squared error behind the regressor's convolution, their gradients) --
+long long hint_partial_rows(int B, int P);
+size_t hint_workspace_bytes(int B, int C, int P);
+hipError_t launch_hint_fwd(const void* x, const void* t, const float* gamma, const float* beta, const float* conv_bias,
+                           float* running_mean, float* running_var, float momentum, float eps, int B, int C, int P, int dt_x,
+                           int lay_x, int dt_t, int lay_t, double* partials, double* mean, double* invstd, double* sums, float* loss,
+                           hipStream_t st);
+hipError_t launch_hint_bwd(const void* x, const void* t, const float* gamma, const float* beta, const double* mean,
+                           const double* invstd, const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta,
+                           int B, int C, int P, int dt_x, int lay_x, int dt_t, int lay_t, hipStream_t st);
+
 // ---- rkd.hip (Relational Knowledge Distillation: pairwise squared distances, the distance and angle terms, the student's gradient) --
 size_t rkd_workspace_bytes(int B);
 hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st);

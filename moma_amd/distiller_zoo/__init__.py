@@ -1,4 +1,5 @@
 from .AT import Attention
+from .FitNet import ConvReg, HintLoss
 from .KD import DistillKL
 from .NST import NSTLoss
 from .PKT import PKT
@@ -6,4 +7,4 @@ from .RKD import RKDLoss
 from .SP import Similarity
 from .VID import VIDLoss
 
-__all__ = ["Attention", "DistillKL", "NSTLoss", "PKT", "RKDLoss", "Similarity", "VIDLoss"]
+__all__ = ["Attention", "ConvReg", "DistillKL", "HintLoss", "NSTLoss", "PKT", "RKDLoss", "Similarity", "VIDLoss"]

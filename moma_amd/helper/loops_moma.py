@@ -46,6 +46,14 @@ no-grad forward with every feature map).  The criterion is a ModuleList with tra
 log_scale per pair): it sits in the optimizer, its regressors run under the step's autocast, its Gaussian likelihood on csrc/vid.hip
 (fp32 / bf16, NCHW / channels_last per side), and its gradients are synchronised across ranks with those of the other trainable
 criteria.  No memory; the step is eager.
+
+`--distill hint` (reference :284-286): the KD term is criterion_kd(*module_list[1](feat_s[hint_layer], feat_t[hint_layer])) -- the
+FitNets hint: module_list[1] is the trained regressor distiller_zoo.ConvReg (convolution -> BatchNorm -> ReLU), criterion_kd a plain
+MSE.  The loop calls `module_list[1].loss(f_s, f_t)`, the same value in one piece: under the step's autocast the convolution runs
+without its bias and BatchNorm, ReLU, the squared error and their backward on csrc/hint.hip (the float64 composite on the CPU and in
+eval mode).  The teacher's map comes from the same eager no-grad forward as `attention`'s.  The regressor sits in the optimizer and
+in the checkpoint (key `regress_s`), and its gradients are synchronised across ranks with those of the other trainable criteria.
+No memory; the step is eager.
 """
 from __future__ import print_function
 
@@ -92,6 +100,7 @@ class MomaStep:
     def __init__(self, module_list, criterion_list, trainer, contrast, optimizer, opt, dev):
         self.criterion_cls, self.criterion_div, self.criterion_kd = criterion_list[0], criterion_list[1], criterion_list[2]
         self.model_s, self.model_t = module_list[0], module_list[-1]
+        self.regress_s = module_list[1] if opt.distill == "hint" else None       # (--distill hint: the trained ConvReg)
         self.trainer, self.contrast, self.optimizer, self.opt, self.dev = trainer, contrast, optimizer, opt, dev
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(getattr(opt, "amp", None))
         self.scaler = getattr(opt, "_grad_scaler", None)
@@ -141,6 +150,10 @@ class MomaStep:
                     else teacher(images, is_feat=True)
                 ft = ft[1:-1] if opt.distill in ("attention", "vid") else ft[1:-2] if opt.distill == "nst" else [ft[-2]]
                 return lt.float(), [f.detach() for f in ft], None                # g_t rides in the key slot
+            if opt.distill == "hint":                                            # (:284-286) feat_t[hint_layer], likewise
+                ft, lt = teacher(images, is_feat=True, full_feats=True) if isinstance(teacher, GraphedInference) \
+                    else teacher(images, is_feat=True)
+                return lt.float(), [ft[opt.hint_layer].detach()], None
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
             return lt.float(), ft[-1].float(), None
@@ -203,6 +216,8 @@ class MomaStep:
             out["g_s"] = list(feat_s[1:-1])                                               # (:146)
         if opt.distill == "similarity":
             out["g_s"] = [feat_s[-2]]                                                     # (:141)
+        if opt.distill == "hint":
+            out["g_s"] = [feat_s[opt.hint_layer]]                                         # (:285)
         if opt.distill == "rkd":
             f_s = feat_s[-1]                                                              # (:156)
         if opt.distill == "pkt":
@@ -271,6 +286,9 @@ class MomaStep:
         if opt.distill == "vid":                                                          # (:145-149) one criterion per pair; g_t rides in fw["k"]
             with self.autocast():                                                         # (the regressors are convolutions)
                 return sum(c(f_s, f_t) for f_s, f_t, c in zip(fw["g_s"], fw["k"], criterion_kd)).float()
+        if opt.distill == "hint":                                                         # (:284-286) regressor + MSE as one value; f_t rides in fw["k"]
+            with self.autocast():                                                         # (the regressor is a convolution)
+                return self.regress_s.loss(fw["g_s"][0], fw["k"][0]).float()
         if opt.distill == "rkd":                                                          # (:155-158) f_t rides in fw["k"]
             return criterion_kd(fw["f_s"], fw["k"]).float()
         if opt.distill == "pkt":                                                          # (:159-162) likewise
@@ -332,6 +350,7 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
 
     criterion_kd = criterion_list[2]
     model_s, model_t = module_list[0], module_list[-1]
+    trained_kd = module_list[1] if opt.distill == "hint" else criterion_kd       # (hint: the regressor trains, the criterion is a plain MSE)
 
     batch_time, losses, top1 = AverageMeter(), AverageMeter(), AverageMeter()
     n_batch = len(train_loader)
@@ -342,19 +361,19 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             if torch.cuda.is_available() else torch.device("cpu")
     step = MomaStep(module_list, criterion_list, trainer, contrast, optimizer, opt, dev)
     single_rank = bool(getattr(trainer, "grad_sync_single_rank", False))
-    sync_criterion = opt.distill in ("moma", "crd", "vid") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
+    sync_criterion = opt.distill in ("moma", "crd", "vid", "hint") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
     flat_dp = isinstance(model_s, FlatDataParallel)
     flat_params = None
     if flat_dp:
         # learning/ddp.py: ONE flat all-reduce per step behind the backward -- the student's gradients and those of the trainable
         # criterion modules (atts_q / embed_s: not under any wrapper, un-synchronised in the reference)
         flat_params = model_s.grad_params()
-        if opt.distill in ("moma", "crd", "vid"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
-            flat_params = flat_params + [p for p in criterion_kd.parameters() if p.requires_grad]
+        if opt.distill in ("moma", "crd", "vid", "hint"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
+            flat_params = flat_params + [p for p in trained_kd.parameters() if p.requires_grad]
     elif sync_criterion:
         # stock DDP on the student: one flat all-reduce per step for the trainable criterion modules, launched from autograd
         # hooks (overlaps the backward)
-        trainer.attach_grad_sync([p for p in criterion_kd.parameters() if p.requires_grad])
+        trainer.attach_grad_sync([p for p in trained_kd.parameters() if p.requires_grad])
     # the teacher's two no-grad forwards per step are replayed from a HIP graph after a few eager calls
     # (opt.graph_teacher, default on for GPU runs; see helper/graphs.py); everything else uses `model_t` itself
     teacher = model_t

@@ -1578,6 +1578,117 @@ def vid_nll(mean, target, log_scale, eps=1e-5) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# FitNets hint: training-mode BatchNorm -> ReLU -> MSE behind the regressor's convolution   (models/util.py ConvReg, distiller_zoo/FitNet.py)
+# ------------------------------------------------------------------------------------------------
+def hint_native(B: int, C: int, P: int, dtype=None, channels_last=None) -> bool:
+    """Shapes [B, C, H W = P] whose BatchNorm -> ReLU -> MSE tail runs on csrc/hint.hip; the others take ConvReg.composite.
+    By profiles/hint_layer_microbench.txt (the five hint_layer maps of EfficientNet-B0 at B = 256, both layouts, fp32 and bf16;
+    verdict: fused <= stock ops + the stock form's own spread; two series) 19 of 20 rows hold at 1.2 - 10 x; 112 x 14 x 14 in fp32
+    NCHW loses in both series, 161.2 against 151.8 us and 209.4 against 178.9 us: the two C-ABI calls take 54 us there, the rest is
+    host work of the op (allocations, argument checks, four launches), which the stock form's three ops undercut on a 135 MB map.
+    That class -- fp32 storage, NCHW, planes of 64 to 255 pixels -- goes to the composite; the same map in bf16 (1.5 - 1.6 x) or
+    channels_last (3.0 x) holds and stays.  `dtype` and `channels_last` describe the convolution's output; asked without them the
+    table answers for the shape alone (True).
+    A shape BatchNorm itself refuses (one value per channel) is not asked here: the op raises for it."""
+    if dtype == torch.float32 and channels_last is False and 64 <= P < 256:
+        return False
+    return True
+
+
+def _hint_side(f, name):
+    """-> layout code of a dense [B,C,H,W] float32 / bfloat16 device tensor (contiguous or channels_last, taken as it lies)"""
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() != 4 or f.dtype not in _DT_CODES:
+        raise TypeError(f"hint_bn_relu_mse: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+    if f.is_contiguous():
+        return _lib.LAYOUT_NCHW
+    if f.is_contiguous(memory_format=torch.channels_last):
+        return _lib.LAYOUT_NHWC
+    raise ValueError(f"hint_bn_relu_mse: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is neither contiguous nor "
+                     "channels_last (use distiller_zoo.ConvReg.composite)")
+
+
+class _HintBNReLUMSE(torch.autograd.Function):
+    """hint_fwd (statistics, running statistics, loss, A and B) in the forward; hint_bwd (dx from the two maps and the saved [C]
+    vectors, d weight and d bias from A and B) in the backward.  conv_bias only moves running_mean: its gradient is exact zeros."""
+
+    @staticmethod
+    def forward(ctx, x, target, weight, bias, running_mean, running_var, momentum, eps, conv_bias):
+        lib = _lib.load()
+        lay_x, lay_t = _hint_side(x, "x"), _hint_side(target, "target")
+        B, Cc, H, W = x.shape
+        vecs = [("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var), ("conv_bias", conv_bias)]
+        for nm, v in vecs:
+            if v is None and nm in ("running_mean", "running_var", "conv_bias"):
+                continue
+            _dev(v, nm, torch.float32)
+            if tuple(v.shape) != (Cc,):
+                raise ValueError(f"hint_bn_relu_mse: {nm} {tuple(v.shape)} for {Cc} channels")
+        if tuple(target.shape) != (B, Cc, H, W):
+            raise ValueError(f"hint_bn_relu_mse: x {tuple(x.shape)} and target {tuple(target.shape)} do not agree")
+        P = H * W
+        if B * P < 2:
+            raise ValueError(f"hint_bn_relu_mse: expected more than 1 value per channel when training, got x {tuple(x.shape)}")
+        dev = x.device
+        codes = (_DT_CODES[x.dtype], lay_x, _DT_CODES[target.dtype], lay_t)
+        with _timed("moma_hint_fwd"):
+            n = lib.moma_hint_workspace_bytes(B, Cc, P, *codes)
+            if n == 0:
+                raise ValueError(f"hint_bn_relu_mse: no workspace for x {tuple(x.shape)}")
+            buf = torch.empty(n // 8 + 4 * Cc, device=dev, dtype=torch.float64)      # (one allocation: workspace, mean, invstd, A and B)
+            ws, mean, invstd, sums = buf[:n // 8], buf[n // 8:n // 8 + Cc], buf[n // 8 + Cc:n // 8 + 2 * Cc], buf[n // 8 + 2 * Cc:]
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            check(lib.moma_hint_fwd(_ptr(x), _ptr(target), _ptr(weight), _ptr(bias), _ptr(conv_bias), _ptr(running_mean),
+                                    _ptr(running_var), float(momentum), float(eps), B, Cc, P, *codes, _ptr(ws), n, _ptr(mean),
+                                    _ptr(invstd), _ptr(sums), _ptr(loss), _stream()), "moma_hint_fwd")
+        ctx.save_for_backward(x, target, weight, bias, mean, invstd, sums)
+        ctx.codes = codes
+        ctx.has_conv_bias = conv_bias is not None
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, target, weight, bias, mean, invstd, sums = ctx.saved_tensors
+        B, Cc, H, W = x.shape
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        need = ctx.needs_input_grad
+        dx = d_w = d_b = None
+        if need[0] or need[2] or need[3]:
+            with _timed("moma_hint_bwd"):
+                if need[0]:
+                    dx = torch.empty_like(x)          # (same dtype, same strides: NCHW or channels_last)
+                if need[2]:
+                    d_w = torch.empty_like(weight)
+                if need[3]:
+                    d_b = torch.empty_like(bias)
+                check(lib.moma_hint_bwd(_ptr(x), _ptr(target), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(invstd), _ptr(sums), _ptr(g),
+                                        _ptr(dx), _ptr(d_w), _ptr(d_b), B, Cc, H * W, *ctx.codes, _stream()), "moma_hint_bwd")
+        d_cb = torch.zeros_like(weight) if (ctx.has_conv_bias and need[8]) else None
+        return dx, None, d_w, d_b, None, None, None, None, d_cb
+
+
+def hint_bn_relu_mse(x, target, weight, bias, running_mean, running_var, momentum, eps, conv_bias=None) -> torch.Tensor:
+    """FitNets hint behind the regressor's convolution: mean((relu(batch_norm(x)) - target)^2) with the BatchNorm in training mode
+    (batch statistics; running_mean / running_var, each optional, updated in place with `momentum`, the variance unbiased).  x (the
+    convolution's output WITHOUT its bias) and target are [B,C,H,W], float32 or bfloat16, contiguous or channels_last, independently
+    per side; weight, bias, the running statistics and conv_bias are [C] float32 -> scalar float32.  conv_bias is the convolution's
+    bias: in front of a training-mode BatchNorm it moves running_mean and nothing else, so it is added there only and its gradient
+    is exact zeros.  Gradients flow to x (in its dtype and strides), weight, bias and conv_bias; the target gets none."""
+    for t, nm in ((x, "x"), (target, "target")):
+        _dev(t, nm, dtype=None, contiguous=False)
+        if t.dim() != 4:
+            raise ValueError(f"hint_bn_relu_mse: {nm} must be [B,C,H,W], got {tuple(t.shape)}")
+    if target.requires_grad and torch.is_grad_enabled():
+        raise ValueError("hint_bn_relu_mse: the kernels give no gradient to the target (detach it, or use "
+                         "distiller_zoo.ConvReg.composite)")
+    if momentum is None:
+        raise ValueError("hint_bn_relu_mse: momentum=None (cumulative average) is served by distiller_zoo.ConvReg.composite")
+    return _HintBNReLUMSE.apply(x, target, weight, bias, running_mean, running_var, float(momentum), float(eps), conv_bias)
+
+
+# ------------------------------------------------------------------------------------------------
 # What the losses on a B x B batch relation (rkd, sp, pkt: below) share: guards, the [B, D] view, the backward call
 # ------------------------------------------------------------------------------------------------
 def _rel_side(op, f, name):

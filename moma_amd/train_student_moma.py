@@ -15,7 +15,10 @@ and launch lines carry over.  What differs:
     ships no launch line for it either, the published one of RepDistiller is `--distill pkt -a 0 -b 30000`), `vid` (Variational
     Information Distillation over the intermediate feature maps: one distiller_zoo/VID.py per pair, its 1 x 1 regressor and per-channel
     log_scale trained with the student, checkpointed and resumed with it, the Gaussian likelihood on the kernels of csrc/vid.hip; the
-    reference ships no launch line for it either, the published one of RepDistiller is `--distill vid -a 0 -b 1`) and `crd` (Contrastive
+    reference ships no launch line for it either, the published one of RepDistiller is `--distill vid -a 0 -b 1`), `hint` (the FitNets
+    hint on feat[--hint_layer]: distiller_zoo/FitNet.py, the regressor ConvReg -- convolution, BatchNorm, ReLU -- trained with the
+    student in module_list[1], checkpointed under `regress_s` and resumed with it, everything behind its convolution on the kernels
+    of csrc/hint.hip; the reference's launch line is `--distill hint -c 1 -d 1 -b 100`) and `crd` (Contrastive
     Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
     `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
     built -- the other comparison criteria are out of scope (SURVEY section 2);
@@ -52,7 +55,7 @@ from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
-from .distiller_zoo import PKT, Attention, DistillKL, NSTLoss, RKDLoss, Similarity, VIDLoss
+from .distiller_zoo import PKT, Attention, ConvReg, DistillKL, HintLoss, NSTLoss, RKDLoss, Similarity, VIDLoss
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
 from .learning.contrast_trainer import ContrastTrainer
@@ -251,6 +254,13 @@ def build_training(opt, device):
         t_n = [f.shape[1] for f in feat_t[1:-1]]
         criterion_kd = nn.ModuleList([VIDLoss(s, t, t) for s, t in zip(s_n, t_n)])
         trainable_list.append(criterion_kd)
+    elif opt.distill == "hint":
+        # reference train_student_moma.py:288-292: the criterion is a plain MSE; the regressor (convolution -> BatchNorm -> ReLU on
+        # feat_s[hint_layer], its weights drawn here) trains with the student and rides in module_list[1]
+        criterion_kd = HintLoss()
+        regress_s = ConvReg(feat_s[opt.hint_layer].shape, feat_t[opt.hint_layer].shape)
+        module_list.append(regress_s)
+        trainable_list.append(regress_s)
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
@@ -385,7 +395,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         # criterion modules and the teacher are under no wrap: the reference relies on identical seeds; one flat
         # broadcast from rank 0 makes it a fact
         from .learning.ddp import broadcast_module_state
-        broadcast_module_state([criterion_list[2], model_t])
+        broadcast_module_state([criterion_list[2], model_t] + ([module_list[1]] if opt.distill == "hint" else []))
     if opt.amp == "fp16":
         opt._grad_scaler = torch.amp.GradScaler("cuda")
     print("opt.batch_size", opt.batch_size)
@@ -409,6 +419,8 @@ def main_worker(gpu, ngpus_per_node, opt):
         model_s.load_state_dict(ck["model"])
         model_t.load_state_dict(ck["model_t"])
         criterion_list[2].load_state_dict(ck["criterion_kd"])
+        if opt.distill == "hint":
+            module_list[1].load_state_dict(ck["regress_s"])             # (the trained regressor, before the optimizer state)
         optimizer.load_state_dict(ck["optimizer"])
         if getattr(opt, "_grad_scaler", None) is not None and ck.get("grad_scaler"):
             opt._grad_scaler.load_state_dict(ck["grad_scaler"])         # (--amp fp16: the loss scale continues where it was)
@@ -431,7 +443,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         print("==> training...")
         t1 = time.time()
         train_acc, train_loss = train_distill_moma(epoch, train_loader, module_list, criterion_list,
-                                                   trainer if opt.distill in ("moma", "crd", "vid") else None, contrast, optimizer, opt)
+                                                   trainer if opt.distill in ("moma", "crd", "vid", "hint") else None, contrast, optimizer, opt)
         if device.type == "cuda":
             torch.cuda.synchronize()
         t2 = time.time()
@@ -470,6 +482,7 @@ def main_worker(gpu, ngpus_per_node, opt):
             # full training state (the reference saves the student only): shared part by the main rank ...
             _atomic_save({"epoch": epoch, "model": model_s.state_dict(), "model_t": model_t.state_dict(),
                           "criterion_kd": criterion_list[2].state_dict(),
+                          **({"regress_s": module_list[1].state_dict()} if opt.distill == "hint" else {}),
                           "contrast": contrast.state_dict() if contrast is not None else None,
                           "optimizer": optimizer.state_dict(), "best_acc": best_acc, "best_f1": best_f1,
                           "grad_scaler": opt._grad_scaler.state_dict() if getattr(opt, "_grad_scaler", None) is not None else None},
