@@ -445,6 +445,56 @@ int moma_sp_gram(const void* f, int B, long long K, int dtype, void* workspace, 
 int moma_sp_terms(const void* workspace_s, size_t workspace_s_bytes, long long Ks, const void* workspace_t, size_t workspace_t_bytes,
                   long long Kt, int B, double* G, double* H, double* rows, double* M, float* loss, moma_stream_t stream);
 int moma_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_s, int B, long long K, int dtype, moma_stream_t stream);
+/* moma_sp_gram_sum  the first half of moma_sp_terms on its own (`--distill semckd`: ops.batch_gram): the workspace of ONE side that
+ *                moma_sp_gram wrote for (B, K) -> G [B, B] fp32 = the split partials added in double in the order of the splits (the
+ *                very sum of moma_sp_terms, one copy of the code), rounded once to fp32.  Both triangles hold the same bits.  With
+ *                the rounding of each split's partial, G lies within (splits + 1) 2^-24 of |X| |X|^T (entry-wise, |.| the absolute
+ *                values) of the product of the stored values; where every partial sum is exact in fp32 it IS that product.  With
+ *                M = dG + dG^T (double) and a device scalar 1, moma_sp_bwd is its backward.  Same guards as moma_sp_terms. */
+int moma_sp_gram_sum(const void* workspace, size_t workspace_bytes, long long K, int B, float* G, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SEMCKD  Cross-Layer Distillation with Semantic Calibration (`--distill semckd`) -- replaces SemCKDLoss.forward
+ *      (distiller_zoo/SemCKD.py: S x T times MSELoss(reduction='none') -> reshape -> mean -> a strided write into ind_loss, then the
+ *      weighted sum) and its autograd backward, for ALL pairs of (student map i, teacher map j) in ONE grouped call each way.
+ *      Pair p = i T + j has x_p (the projection's output) and t_p (the pooled teacher map), both [B, n_p], n_p = C h w; with the
+ *      attention w [B,S,T] fp32:
+ *          ind[b,p]  = (1/n_p) sum_k (x_p[b,k] - t_p[b,k])^2
+ *          loss      = (1/(B S)) sum_b sum_p w[b,p] ind[b,p]
+ *          dx_p[b,k] = g_loss 2 w[b,p] / (n_p B S) (x_p[b,k] - t_p[b,k])        (in x_p's dtype)
+ *          dw[b,p]   = g_loss ind[b,p] / (B S)                                  (left to the caller: a multiply of ind)
+ *      Both maps of a pair lie on a common grid and in the SAME memory format; each side is read in storage order as B rows of n_p
+ *      elements (dense, row stride n_p), NCHW and channels_last alike: the sum of squares does not depend on the order of the
+ *      columns, and dx_p is written in that order.  No layout flag exists.  Per side and per pair the dtype is MOMA_DT_F32 or
+ *      MOMA_DT_BF16, the pointers aligned to the element size (16-byte accesses where the base addresses of the pair and n_p allow,
+ *      element accesses otherwise).  The difference and the square are fp32, every sum double; a bf16 dx is rounded from the fp32
+ *      value.  No atomics: bitwise reproducible.  t gets no gradient.
+ *      `pairs` is a HOST array, read during the call (as moma_infonce_fused_multi and moma_mha_fwd_fast read theirs).
+ *
+ * workspace        moma_semckd_workspace_bytes() = B sum_p ceil(n_p / MOMA_SEMCKD_CHUNK) 8 bytes: one double per work item (pair,
+ *                  sample, chunk of MOMA_SEMCKD_CHUNK elements).  The pairs differ widely in n_p, so the launches run over this flat
+ *                  list (the host fills a prefix table of chunk counts, a workgroup finds its pair in it), not over a grid of pairs.
+ *                  8-byte aligned.  0 for arguments moma_semckd_fwd refuses.
+ * moma_semckd_fwd  one read of every x_p and t_p -> ind [B,S,T] fp32, loss [1] fp32.  Two launches: the streaming one writes one
+ *                  double partial per item, the finalize one adds the partials of a (b,p) in chunk order.  `dx` is ignored.
+ * moma_semckd_bwd  one launch over the same list: writes every non-null pairs[p].dx, with no reduction of its own.  g_loss is a
+ *                  DEVICE scalar (the upstream gradient of the loss, e.g. a GradScaler factor): nothing is read back to the host.
+ *      n_pairs outside 1 .. MOMA_SEMCKD_MAX_PAIRS, S < 1, n_pairs % S != 0, B < 1 or any n_p < 1: MOMA_E_SHAPE; an unknown dtype:
+ *      MOMA_E_UNSUPPORTED; nothing is launched and nothing written in either case.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_SEMCKD_MAX_PAIRS = 64, MOMA_SEMCKD_CHUNK = 4096 };
+typedef struct moma_semckd_pair {
+    const void* x;         /* [B, n] dtype_x */
+    const void* t;         /* [B, n] dtype_t */
+    void* dx;              /* [B, n] dtype_x out (moma_semckd_bwd) or NULL */
+    long long n;           /* elements of one sample: C h w */
+    int dtype_x, dtype_t;  /* MOMA_DT_* */
+} moma_semckd_pair_t;
+size_t moma_semckd_workspace_bytes(const moma_semckd_pair_t* pairs, int n_pairs, int B);
+int moma_semckd_fwd(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, const float* w, void* workspace,
+                    size_t workspace_bytes, float* ind, float* loss, moma_stream_t stream);
+int moma_semckd_bwd(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, const float* w, const float* g_loss,
+                    moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PKT  Probabilistic Knowledge Transfer (`--distill pkt`) on one pair of feature rows -- replaces PKT.cosine_similarity_loss

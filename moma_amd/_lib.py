@@ -20,6 +20,7 @@ HINT_CHUNK = 1024
 RKD_MAX_B = 1024
 SP_MAX_B = 1024
 PKT_MAX_B = 1024
+SEMCKD_MAX_PAIRS, SEMCKD_CHUNK = 64, 4096
 MHA_SAVE_PROBS, MHA_SAVE_LSE = 0, 1
 ABI_VERSION = 4
 EMA_BLOCK_ELEMS = 4096
@@ -78,6 +79,10 @@ SIGNATURES = {
     "moma_sp_gram": (_i, [_p, _i, _l, _i, _p, _z, _p]),
     "moma_sp_terms": (_i, [_p, _z, _l, _p, _z, _l, _i, _p, _p, _p, _p, _p, _p]),
     "moma_sp_bwd": (_i, [_p, _p, _p, _p, _i, _l, _i, _p]),
+    "moma_sp_gram_sum": (_i, [_p, _z, _l, _i, _p, _p]),
+    "moma_semckd_workspace_bytes": (_z, [_p, _i, _i]),
+    "moma_semckd_fwd": (_i, [_p, _i, _i, _i, _p, _p, _z, _p, _p, _p]),
+    "moma_semckd_bwd": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "moma_pkt_workspace_bytes": (_z, [_i]),
     "moma_pkt_gram": (_i, [_p, _i, _i, _i, _p, _p]),
     "moma_pkt_gram_pair": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
@@ -127,6 +132,11 @@ class MhaModule(C.Structure):
     """moma_mha_module_t of include/moma_hip.h (one module of a grouped moma_mha_fwd_fast call)."""
     _fields_ = [("x", _p), ("pack", _p), ("b_qkv", _p), ("b_proj", _p), ("y", _p), ("qkv16", _p), ("attn16", _p),
                 ("lse", _p), ("qpack", _p), ("qpack_scale", _f), ("x_dtype", _i)]
+
+
+class SemckdPair(C.Structure):
+    """moma_semckd_pair_t of include/moma_hip.h (one (student, teacher) pair of a grouped moma_semckd_fwd / _bwd call)."""
+    _fields_ = [("x", _p), ("t", _p), ("dx", _p), ("n", C.c_longlong), ("dtype_x", _i), ("dtype_t", _i)]
 
 
 _lib = None

@@ -1049,6 +1049,59 @@ int moma_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF_
     return hip_rc(launch_sp_bwd(f_s, M, g_loss, dF_s, B, K, dtype, (hipStream_t)stream));
 }
 
+int moma_sp_gram_sum(const void* workspace, size_t workspace_bytes, long long K, int B, float* G, moma_stream_t stream) {
+    if (!workspace || !G) return MOMA_E_NULL;
+    const int rc = sp_check(B, K, MOMA_DT_F32);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < sp_workspace_bytes(B, K)) return MOMA_E_WORKSPACE;
+    if (misaligned(workspace, 4) || misaligned(G, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_sp_gram_sum((const float*)workspace, (int)sp_splits(B, K), B, G, (hipStream_t)stream));
+}
+
+// ---- SemCKD: the grouped weighted per-sample MSE ----------------------------------------------------------------------------------
+static int semckd_check(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, bool with_dx) {
+    if (!pairs) return MOMA_E_NULL;
+    if (n_pairs < 1 || n_pairs > MOMA_SEMCKD_MAX_PAIRS || S < 1 || n_pairs % S != 0 || B < 1) return MOMA_E_SHAPE;
+    for (int p = 0; p < n_pairs; ++p)
+        if (pairs[p].n < 1) return MOMA_E_SHAPE;
+    for (int p = 0; p < n_pairs; ++p)
+        if (bad_dt(pairs[p].dtype_x) || bad_dt(pairs[p].dtype_t)) return MOMA_E_UNSUPPORTED;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (!pairs[p].x || !pairs[p].t) return MOMA_E_NULL;
+        const size_t ex = pairs[p].dtype_x == MOMA_DT_BF16 ? 2 : 4;
+        if (misaligned(pairs[p].x, ex) || misaligned(pairs[p].t, pairs[p].dtype_t == MOMA_DT_BF16 ? 2 : 4) ||
+            (with_dx && misaligned(pairs[p].dx, ex)))
+            return MOMA_E_ALIGN;
+    }
+    return MOMA_OK;
+}
+
+size_t moma_semckd_workspace_bytes(const moma_semckd_pair_t* pairs, int n_pairs, int B) {
+    if (!pairs || n_pairs < 1 || n_pairs > MOMA_SEMCKD_MAX_PAIRS || B < 1) return 0;
+    for (int p = 0; p < n_pairs; ++p)
+        if (pairs[p].n < 1) return 0;
+    return semckd_workspace_bytes(pairs, n_pairs, B);
+}
+
+int moma_semckd_fwd(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, const float* w, void* workspace,
+                    size_t workspace_bytes, float* ind, float* loss, moma_stream_t stream) {
+    if (!w || !workspace || !ind || !loss) return MOMA_E_NULL;
+    const int rc = semckd_check(pairs, n_pairs, S, B, false);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < semckd_workspace_bytes(pairs, n_pairs, B)) return MOMA_E_WORKSPACE;
+    if (misaligned(w, 4) || misaligned(workspace, 8) || misaligned(ind, 4) || misaligned(loss, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_semckd_fwd(pairs, n_pairs, S, B, w, (double*)workspace, ind, loss, (hipStream_t)stream));
+}
+
+int moma_semckd_bwd(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, const float* w, const float* g_loss,
+                    moma_stream_t stream) {
+    if (!w || !g_loss) return MOMA_E_NULL;
+    const int rc = semckd_check(pairs, n_pairs, S, B, true);
+    if (rc != MOMA_OK) return rc;
+    if (misaligned(w, 4) || misaligned(g_loss, 4)) return MOMA_E_ALIGN;
+    return hip_rc(launch_semckd_bwd(pairs, n_pairs, S, B, w, g_loss, (hipStream_t)stream));
+}
+
 // ---- Probabilistic Knowledge Transfer ---------------------------------------------------------------------------------------------
 size_t moma_pkt_workspace_bytes(int B) {
     if (B < 1 || B > MOMA_PKT_MAX_B) return 0;

@@ -189,15 +189,15 @@ static_assert(pick_vec(6, 2, 0, {8, 4, 2}) == 2 && pick_vec(112, 2, 4, {8, 4, 2}
 // nst.hip, rkd.hip, sp.hip {16 / eb}: 16 bytes or nothing
 static_assert(pick_vec(12, 2, 0, {8}) == 1 && pick_vec(16, 2, 0, {8}) == 8 && pick_vec(16, 2, 8, {8}) == 1, "nst / rkd / sp");
 
-// ---- run-time (dtype, vec) -> template arguments (host) ----------------------------------------------------------------------
+// ---- run-time (dtype, vec) -> template arguments (host; semckd.hip also on the device, per pair of a grouped launch) ---------
 // f(TypeTag<bf16_raw>{}) or f(TypeTag<float>{}) by MOMA_DT_*; inside a generic lambda: using T = typename decltype(t)::type
 template <typename T> struct TypeTag { using type = T; };
-template <typename F> auto with_dtype(int dtype, F&& f) {
+template <typename F> __host__ __device__ auto with_dtype(int dtype, F&& f) {
     return dtype == MOMA_DT_BF16 ? f(TypeTag<bf16_raw>{}) : f(TypeTag<float>{});
 }
 // f(std::integral_constant<int, V>{}) for the V of the list V, REST... (widest first) that equals `vec`, the last one for any other
 // `vec`.  Widths above CAP (at most call sites MAXVEC<T>) are left out of the list: they get no instantiation.
-template <int CAP, int V, int... REST, typename F> void with_vec(int vec, F&& f) {
+template <int CAP, int V, int... REST, typename F> __host__ __device__ void with_vec(int vec, F&& f) {
     if constexpr (V > CAP) with_vec<CAP, REST...>(vec, f);
     else if constexpr (sizeof...(REST) == 0) f(std::integral_constant<int, V>{});
     else if (vec == V) f(std::integral_constant<int, V>{});
@@ -317,6 +317,14 @@ hipError_t launch_sp_gram(const void* f, int B, long long K, int dtype, float* P
 hipError_t launch_sp_terms(const float* P_s, int splits_s, const float* P_t, int splits_t, int B, double* G, double* H, double* rows,
                            double* M, float* loss, hipStream_t st);
 hipError_t launch_sp_bwd(const void* f_s, const double* M, const float* g_loss, void* dF, int B, long long K, int dtype, hipStream_t st);
+hipError_t launch_sp_gram_sum(const float* P, int splits, int B, float* G, hipStream_t st);
+
+// ---- semckd.hip (SemCKD: the attention-weighted per-sample MSE of every (student, teacher) pair as one grouped call each way) -------
+size_t semckd_workspace_bytes(const moma_semckd_pair_t* pairs, int n_pairs, int B);
+hipError_t launch_semckd_fwd(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, const float* w, double* partials, float* ind,
+                             float* loss, hipStream_t st);
+hipError_t launch_semckd_bwd(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, const float* w, const float* g_loss,
+                             hipStream_t st);
 
 // ---- pkt.hip (Probabilistic Knowledge Transfer: the raw batch Gram per side in double, the cosine / KL terms, the student's gradient) --
 size_t pkt_workspace_bytes(int B);

@@ -21,6 +21,8 @@
 //               sum of (H^t - H^s)^2; the sums over the workgroup: block_sum of batchrel.hpp.       50 VGPRs, LDS 32 B
 //     sp_m      grid ceil(B / 16)^2: M_ij = Q_ij + Q_ji (the same sum for (i, j) and (j, i): symmetric bit for bit).   24 VGPRs
 //     sp_final  one workgroup adds the B row sums in a fixed order (array_sum of batchrel.hpp) -> loss (fp32).   13 VGPRs, LDS 32 B
+//   sp_gram_sum  (moma_sp_gram_sum, `--distill semckd`: ops.batch_gram) G of ONE side on its own as fp32: sp_rows' sum of the split
+//             partials (sp_split_sum: one copy), one thread per entry, grid ceil(B^2 / 256).
 //   sp_bwd    grid (ceil(K / 64), ceil(B / 128)): dF_s[128 rows, 64 columns] = g M X[:, 64 columns] on v_mfma_f32_32x32x2_f32 for both
 //             storages (bf16 widened while it is staged; M rounded to fp32 once per use: every workgroup reads its
 //             [128, B] block of M as double and converts it -- B^2 8 bytes of L2 reads per 64 columns, 0.5 GB at B = 256, K = 62720,
@@ -143,6 +145,23 @@ __global__ __launch_bounds__(REL_THREADS) void sp_gram_kernel(const T* __restric
     }
 }
 
+// entry o of G: the split partials added in double in the order 0, 1, ...  (unrolled: the loads of eight splits are in flight
+// together, the additions keep the order; one load per addition made sp_rows 234 us at B = 64, K = 62720, where 64 workgroups
+// add 490 partials per side).  THE sum of sp_rows (moma_sp_terms) and of sp_gram_sum (moma_sp_gram_sum)
+__device__ __forceinline__ double sp_split_sum(const float* __restrict__ P, int splits, size_t BB, size_t o) {
+    double g = 0.0;
+#pragma unroll 8
+    for (int s = 0; s < splits; ++s) g += (double)P[s * BB + o];
+    return g;
+}
+
+// grid ceil(B^2 / 256): G [B, B] fp32 of one side.  The partials are symmetric bit for bit and every entry adds them in the same
+// order, so G is
+__global__ __launch_bounds__(REL_THREADS) void sp_gram_sum_kernel(const float* __restrict__ P, int splits, int B, float* __restrict__ G) {
+    const size_t BB = (size_t)B * B, o = (size_t)blockIdx.x * REL_THREADS + threadIdx.x;
+    if (o < BB) G[o] = (float)sp_split_sum(P, splits, BB, o);
+}
+
 // grid B: row i of both sides.  rows = [n_s | n_t | r | lp], each [B]
 __global__ __launch_bounds__(REL_THREADS) void sp_rows_kernel(const float* __restrict__ Ps, int splits_s, const float* __restrict__ Pt,
                                                               int splits_t, int B, double* __restrict__ G, double* __restrict__ H,
@@ -159,12 +178,8 @@ __global__ __launch_bounds__(REL_THREADS) void sp_rows_kernel(const float* __res
         gt[u] = 0.0;
         if (j < B) {
             const size_t o = (size_t)i * B + j;
-            // (unrolled: the loads of eight splits are in flight together, the additions keep the order 0, 1, ...; one load per
-            //  addition made this kernel 234 us at B = 64, K = 62720, where 64 workgroups add 490 partials per side)
-#pragma unroll 8
-            for (int s = 0; s < splits_s; ++s) gs[u] += (double)Ps[s * BB + o];
-#pragma unroll 8
-            for (int s = 0; s < splits_t; ++s) gt[u] += (double)Pt[s * BB + o];
+            gs[u] = sp_split_sum(Ps, splits_s, BB, o);
+            gt[u] = sp_split_sum(Pt, splits_t, BB, o);
             G[o] = gs[u];
             G[BB + o] = gt[u];
             qs = fma(gs[u], gs[u], qs);
@@ -314,6 +329,12 @@ hipError_t launch_sp_gram(const void* f, int B, long long K, int dtype, float* P
         hipLaunchKernelGGL(sp_gram_kernel<T>, grid, dim3(REL_THREADS), 0, st, (const T*)f, P, B, K, vec, nt, per, slabs);
         return hipGetLastError();
     });
+}
+
+hipError_t launch_sp_gram_sum(const float* P, int splits, int B, float* G, hipStream_t st) {
+    const size_t BB = (size_t)B * B;
+    hipLaunchKernelGGL(sp_gram_sum_kernel, dim3((unsigned)((BB + REL_THREADS - 1) / REL_THREADS)), dim3(REL_THREADS), 0, st, P, splits, B, G);
+    return hipGetLastError();
 }
 
 hipError_t launch_sp_terms(const float* P_s, int splits_s, const float* P_t, int splits_t, int B, double* G, double* H, double* rows,

@@ -4,7 +4,9 @@ from .KD import DistillKL
 from .NST import NSTLoss
 from .PKT import PKT
 from .RKD import RKDLoss
+from .SemCKD import MLPEmbed, Proj, SelfA, SemCKDLoss
 from .SP import Similarity
 from .VID import VIDLoss
 
-__all__ = ["Attention", "ConvReg", "DistillKL", "HintLoss", "NSTLoss", "PKT", "RKDLoss", "Similarity", "VIDLoss"]
+__all__ = ["Attention", "ConvReg", "DistillKL", "HintLoss", "MLPEmbed", "NSTLoss", "PKT", "Proj", "RKDLoss", "SelfA", "SemCKDLoss",
+           "Similarity", "VIDLoss"]

@@ -54,6 +54,15 @@ without its bias and BatchNorm, ReLU, the squared error and their backward on cs
 eval mode).  The teacher's map comes from the same eager no-grad forward as `attention`'s.  The regressor sits in the optimizer and
 in the checkpoint (key `regress_s`), and its gradients are synchronised across ranks with those of the other trainable criteria.
 No memory; the step is eager.
+
+`--distill semckd` (reference :101-102, :177-179): the KD term is criterion_kd(*module_list[1](feat_s[1:-1], feat_t[1:-1])) -- Cross-Layer
+Distillation with Semantic Calibration: module_list[1] is the trained distiller_zoo.SelfA (query / key heads on the batch Gram
+matrices, one projection per (student map, teacher map) pair), criterion_kd the weighted sum of the per-sample errors.  The loop calls
+`module_list[1].loss(feat_s[1:-1], feat_t[1:-1])`, the same value in one piece: the Gram matrices on csrc/sp.hip, the head in fp32,
+every pair's weighted error and its backward in ONE grouped call each on csrc/semckd.hip (the float64 composite on the CPU).  SelfA is
+built for one batch size: a shorter last batch is skipped before the step, as in the reference.  The module sits in the optimizer
+and in the checkpoint (key `self_attention`), and its gradients are synchronised across ranks with those of the other trainable
+criteria (the unused `regressor` of its MLPEmbed heads never gets a gradient: both exchanges skip such parameters).  The step is eager.
 """
 from __future__ import print_function
 
@@ -101,6 +110,7 @@ class MomaStep:
         self.criterion_cls, self.criterion_div, self.criterion_kd = criterion_list[0], criterion_list[1], criterion_list[2]
         self.model_s, self.model_t = module_list[0], module_list[-1]
         self.regress_s = module_list[1] if opt.distill == "hint" else None       # (--distill hint: the trained ConvReg)
+        self.self_attention = module_list[1] if opt.distill == "semckd" else None  # (--distill semckd: the trained SelfA)
         self.trainer, self.contrast, self.optimizer, self.opt, self.dev = trainer, contrast, optimizer, opt, dev
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(getattr(opt, "amp", None))
         self.scaler = getattr(opt, "_grad_scaler", None)
@@ -145,10 +155,10 @@ class MomaStep:
         """teacher forward #1 (:270-272), then the moma branch's no-grad part (:309-320, :327-329)."""
         opt, trainer, criterion_kd, model_t = self.opt, self.trainer, self.criterion_kd, self.model_t
         with self.autocast(), torch.no_grad():
-            if opt.distill in ("attention", "nst", "similarity", "vid"):    # (:270-272, :287-292 / :150-154 / :140-144 / :145-149) every feature map, as autocast left it: an eager forward
+            if opt.distill in ("attention", "nst", "similarity", "vid", "semckd"):    # (:270-272, :287-292 / :150-154 / :140-144 / :145-149) every feature map, as autocast left it: an eager forward
                 ft, lt = teacher(images, is_feat=True, full_feats=True) if isinstance(teacher, GraphedInference) \
                     else teacher(images, is_feat=True)
-                ft = ft[1:-1] if opt.distill in ("attention", "vid") else ft[1:-2] if opt.distill == "nst" else [ft[-2]]
+                ft = ft[1:-1] if opt.distill in ("attention", "vid", "semckd") else ft[1:-2] if opt.distill == "nst" else [ft[-2]]
                 return lt.float(), [f.detach() for f in ft], None                # g_t rides in the key slot
             if opt.distill == "hint":                                            # (:284-286) feat_t[hint_layer], likewise
                 ft, lt = teacher(images, is_feat=True, full_feats=True) if isinstance(teacher, GraphedInference) \
@@ -218,6 +228,8 @@ class MomaStep:
             out["g_s"] = [feat_s[-2]]                                                     # (:141)
         if opt.distill == "hint":
             out["g_s"] = [feat_s[opt.hint_layer]]                                         # (:285)
+        if opt.distill == "semckd":
+            out["g_s"] = list(feat_s[1:-1])                                               # (:178)
         if opt.distill == "rkd":
             f_s = feat_s[-1]                                                              # (:156)
         if opt.distill == "pkt":
@@ -289,6 +301,9 @@ class MomaStep:
         if opt.distill == "hint":                                                         # (:284-286) regressor + MSE as one value; f_t rides in fw["k"]
             with self.autocast():                                                         # (the regressor is a convolution)
                 return self.regress_s.loss(fw["g_s"][0], fw["k"][0]).float()
+        if opt.distill == "semckd":                                                       # (:177-179) SelfA + SemCKDLoss as one value; g_t rides in fw["k"]
+            with self.autocast():                                                         # (the projections are convolutions)
+                return self.self_attention.loss(fw["g_s"], fw["k"]).float()
         if opt.distill == "rkd":                                                          # (:155-158) f_t rides in fw["k"]
             return criterion_kd(fw["f_s"], fw["k"]).float()
         if opt.distill == "pkt":                                                          # (:159-162) likewise
@@ -350,7 +365,7 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
 
     criterion_kd = criterion_list[2]
     model_s, model_t = module_list[0], module_list[-1]
-    trained_kd = module_list[1] if opt.distill == "hint" else criterion_kd       # (hint: the regressor trains, the criterion is a plain MSE)
+    trained_kd = module_list[1] if opt.distill in ("hint", "semckd") else criterion_kd   # (hint, semckd: module_list[1] trains, the criterion has no state)
 
     batch_time, losses, top1 = AverageMeter(), AverageMeter(), AverageMeter()
     n_batch = len(train_loader)
@@ -361,14 +376,14 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             if torch.cuda.is_available() else torch.device("cpu")
     step = MomaStep(module_list, criterion_list, trainer, contrast, optimizer, opt, dev)
     single_rank = bool(getattr(trainer, "grad_sync_single_rank", False))
-    sync_criterion = opt.distill in ("moma", "crd", "vid", "hint") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
+    sync_criterion = opt.distill in ("moma", "crd", "vid", "hint", "semckd") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
     flat_dp = isinstance(model_s, FlatDataParallel)
     flat_params = None
     if flat_dp:
         # learning/ddp.py: ONE flat all-reduce per step behind the backward -- the student's gradients and those of the trainable
         # criterion modules (atts_q / embed_s: not under any wrapper, un-synchronised in the reference)
         flat_params = model_s.grad_params()
-        if opt.distill in ("moma", "crd", "vid", "hint"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
+        if opt.distill in ("moma", "crd", "vid", "hint", "semckd"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
             flat_params = flat_params + [p for p in trained_kd.parameters() if p.requires_grad]
     elif sync_criterion:
         # stock DDP on the student: one flat all-reduce per step for the trainable criterion modules, launched from autograd
@@ -412,6 +427,8 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             contrast_idx = contrast_idx.to(dev, non_blocking=True)
         else:
             images, labels = data
+        if opt.distill == "semckd" and images.shape[0] < opt.batch_size:          # (:101-102) SelfA is built for one batch size
+            continue
         images = images.to(dev, non_blocking=True)
         labels = labels.to(dev, non_blocking=True)
         if getattr(opt, "channels_last", False):

@@ -1855,6 +1855,152 @@ def sp_loss(f_s, f_t) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# SemCKD: batch Gram of one map, and the attention-weighted per-sample MSE of all (student, teacher) pairs as one grouped call
+# (models/util.py SelfA, distiller_zoo/SemCKD.py, helper/loops_moma.py:177-179)
+# ------------------------------------------------------------------------------------------------
+class _BatchGram(torch.autograd.Function):
+    """sp_gram -> sp_gram_sum (G = X X^T, fp32) in the forward; sp_bwd with M = dG + dG^T in double and a device scalar 1 in the
+    backward (dX = (dG + dG^T) X, in storage order)."""
+
+    @staticmethod
+    def forward(ctx, f):
+        lib = _lib.load()
+        B, dev = f.shape[0], f.device
+        K = f.numel() // B
+        with _timed("moma_batch_gram_fwd"):
+            n = lib.moma_sp_workspace_bytes(B, K)
+            if n == 0:
+                raise ValueError(f"batch_gram: the kernels take 1 .. {_lib.SP_MAX_B} rows, got {B}")
+            ws = torch.empty(n // 4, device=dev, dtype=torch.float32)
+            G = torch.empty(B, B, device=dev, dtype=torch.float32)
+            check(lib.moma_sp_gram(_ptr(f), B, K, _DT_CODES[f.dtype], _ptr(ws), n, _stream()), "moma_sp_gram")
+            check(lib.moma_sp_gram_sum(_ptr(ws), n, K, B, _ptr(G), _stream()), "moma_sp_gram_sum")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(f)
+        return G
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dG):
+        f, = ctx.saved_tensors
+        dG = dG.to(torch.float64)
+        M = (dG + dG.t()).contiguous()
+        one = torch.ones((), device=f.device, dtype=torch.float32)
+        return _rel_backward("sp", f, M, one, f.shape, f.stride())
+
+
+def batch_gram(f) -> torch.Tensor:
+    """G = X X^T [B, B] float32 of f [B, ...] read as X [B, K] (float32 or bfloat16, contiguous or channels_last, 1 <= B <= 1024): the
+    split-K Gram kernel of csrc/sp.hip and the sum of its partials in double.  The map is read in storage order (G does not depend
+    on the order of the columns); the gradient (dG + dG^T) X comes in f's dtype and strides."""
+    _dev(f, "f", dtype=None, contiguous=False)
+    if f.dim() < 2 or f.dtype not in _DT_CODES:
+        raise TypeError(f"batch_gram: f must be a float32 / bfloat16 tensor [B, ...], got {tuple(f.shape)} {f.dtype}")
+    if f.numel() == 0:
+        raise ValueError(f"batch_gram: f is empty: {tuple(f.shape)}")
+    if not sp_dense(f):
+        raise ValueError("batch_gram: f must be dense with the same strides in every sample (contiguous or channels_last), got "
+                         f"strides {tuple(f.stride())} for {tuple(f.shape)}")
+    if f.shape[0] > _lib.SP_MAX_B:
+        raise ValueError(f"batch_gram: the kernels take 1 .. {_lib.SP_MAX_B} rows, got {f.shape[0]}")
+    return _BatchGram.apply(f)
+
+
+def _semckd_table(xs, ts, dxs):
+    """-> the host array of moma_semckd_pair_t for the pairs (xs[p], ts[p]) with the gradients dxs[p] (None: no gradient wanted)"""
+    tab = (_lib.SemckdPair * len(xs))()
+    for p, (x, t, dx) in enumerate(zip(xs, ts, dxs)):
+        tab[p] = _lib.SemckdPair(x.data_ptr(), t.data_ptr(), 0 if dx is None else dx.data_ptr(), x.numel() // x.shape[0],
+                                 _DT_CODES[x.dtype], _DT_CODES[t.dtype])
+    return tab
+
+
+class _SemCKDWeightedMSE(torch.autograd.Function):
+    """semckd_fwd (ind, loss) over all pairs in the forward; semckd_bwd (every dx) in the backward, d weight = g ind / (B S)."""
+
+    @staticmethod
+    def forward(ctx, weight, n_pairs, *maps):
+        lib = _lib.load()
+        xs, ts = maps[:n_pairs], maps[n_pairs:]
+        B, S, T = weight.shape
+        dev = weight.device
+        with _timed("moma_semckd_fwd"):
+            tab = _semckd_table(xs, ts, [None] * n_pairs)
+            n = lib.moma_semckd_workspace_bytes(tab, n_pairs, B)
+            if n == 0:
+                raise ValueError(f"semckd_weighted_mse: no workspace for {n_pairs} pairs at B = {B}")
+            buf = torch.empty(n // 8 + (B * n_pairs + 2) // 2, device=dev, dtype=torch.float64)   # (one allocation: workspace, ind, loss)
+            ws, tail = buf[:n // 8], buf[n // 8:].view(torch.float32)
+            ind, loss = tail[:B * n_pairs].view(B, S, T), tail[B * n_pairs:B * n_pairs + 1].view(())
+            check(lib.moma_semckd_fwd(tab, n_pairs, S, B, _ptr(weight), _ptr(ws), n, _ptr(ind), _ptr(loss), _stream()),
+                  "moma_semckd_fwd")
+        ctx.save_for_backward(weight, ind, *maps)
+        ctx.n_pairs = n_pairs
+        ctx.mark_non_differentiable(ind)
+        return loss, ind
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_ind):
+        lib = _lib.load()
+        weight, ind = ctx.saved_tensors[:2]
+        n_pairs = ctx.n_pairs
+        maps = ctx.saved_tensors[2:]
+        xs, ts = maps[:n_pairs], maps[n_pairs:]
+        B, S, T = weight.shape
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        need = ctx.needs_input_grad
+        dxs = [torch.empty_like(x) if need[2 + p] else None for p, x in enumerate(xs)]   # (same dtype, same strides)
+        if any(dx is not None for dx in dxs):
+            with _timed("moma_semckd_bwd"):
+                tab = _semckd_table(xs, ts, dxs)
+                check(lib.moma_semckd_bwd(tab, n_pairs, S, B, _ptr(weight), _ptr(g), _stream()), "moma_semckd_bwd")
+        dw = ind * (g / float(B * S)) if need[0] else None
+        return (dw, None, *dxs, *([None] * n_pairs))
+
+
+def semckd_native(n_pairs: int) -> bool:
+    """Whether a group of `n_pairs` pairs runs on csrc/semckd.hip (one call): up to MOMA_SEMCKD_MAX_PAIRS; larger groups take
+    distiller_zoo.SelfA.composite."""
+    return 1 <= n_pairs <= _lib.SEMCKD_MAX_PAIRS
+
+
+def semckd_weighted_mse(s_values, targets, weight):
+    """The tail of SemCKD over ALL pairs in one call: s_values[i][j] (the projection of student map i for teacher map j) and
+    targets[i][j] (teacher map j on the common grid), S lists of T tensors [B, C, h, w] each (float32 or bfloat16 per tensor, the two
+    maps of a pair of one shape and one memory format, contiguous or channels_last), weight [B, S, T] float32 ->
+    (loss, ind): ind[b,i,j] = mean_k (s - t)^2 float32, loss = sum(weight * ind) / (B S) scalar float32.
+    Gradients flow to every s_value (in its dtype and strides) and to weight; targets get none, ind is not differentiable."""
+    S, T = len(s_values), len(s_values[0])
+    xs = [x for row in s_values for x in row]
+    ts = [t for row in targets for t in row]
+    if len(targets) != S or any(len(r) != T for r in s_values) or any(len(r) != T for r in targets):
+        raise ValueError("semckd_weighted_mse: s_values and targets must be S lists of T tensors each")
+    _dev(weight, "weight", torch.float32)
+    if tuple(weight.shape[1:]) != (S, T) or weight.dim() != 3:
+        raise ValueError(f"semckd_weighted_mse: weight {tuple(weight.shape)} for {S} x {T} pairs")
+    if not semckd_native(S * T):
+        raise ValueError(f"semckd_weighted_mse: the kernels take 1 .. {_lib.SEMCKD_MAX_PAIRS} pairs, got {S * T} (use "
+                         "distiller_zoo.SelfA.composite)")
+    B = weight.shape[0]
+    for p, (x, t) in enumerate(zip(xs, ts)):
+        for f, nm in ((x, f"s_values[{p // T}][{p % T}]"), (t, f"targets[{p // T}][{p % T}]")):
+            _dev(f, nm, dtype=None, contiguous=False)
+            if f.dtype not in _DT_CODES or f.dim() < 2 or f.shape[0] != B or f.numel() == 0:
+                raise TypeError(f"semckd_weighted_mse: {nm} must be a float32 / bfloat16 tensor [{B}, ...], got {tuple(f.shape)} {f.dtype}")
+            if not sp_dense(f):
+                raise ValueError(f"semckd_weighted_mse: {nm} must be contiguous or channels_last, got strides {tuple(f.stride())} "
+                                 f"for {tuple(f.shape)} (use distiller_zoo.SelfA.composite)")
+        if x.shape != t.shape or any(e != 1 and a != b for e, a, b in zip(x.shape, x.stride(), t.stride())):
+            raise ValueError(f"semckd_weighted_mse: pair {p}: s_value {tuple(x.shape)} / {tuple(x.stride())} and target "
+                             f"{tuple(t.shape)} / {tuple(t.stride())} must share shape and memory format")
+        if t.requires_grad and torch.is_grad_enabled():
+            raise ValueError("semckd_weighted_mse: the kernels give no gradient to a target (detach it, or use "
+                             "distiller_zoo.SelfA.composite)")
+    return _SemCKDWeightedMSE.apply(weight, S * T, *xs, *ts)
+
+
+# ------------------------------------------------------------------------------------------------
 # Probabilistic Knowledge Transfer: cosine Gram of a batch as row distributions, their KL   (distiller_zoo/PKT.py, helper/loops_moma.py:159-162)
 # ------------------------------------------------------------------------------------------------
 class _PKTLoss(torch.autograd.Function):

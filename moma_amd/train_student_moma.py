@@ -18,7 +18,12 @@ and launch lines carry over.  What differs:
     reference ships no launch line for it either, the published one of RepDistiller is `--distill vid -a 0 -b 1`), `hint` (the FitNets
     hint on feat[--hint_layer]: distiller_zoo/FitNet.py, the regressor ConvReg -- convolution, BatchNorm, ReLU -- trained with the
     student in module_list[1], checkpointed under `regress_s` and resumed with it, everything behind its convolution on the kernels
-    of csrc/hint.hip; the reference's launch line is `--distill hint -c 1 -d 1 -b 100`) and `crd` (Contrastive
+    of csrc/hint.hip; the reference's launch line is `--distill hint -c 1 -d 1 -b 100`), `semckd` (Cross-Layer Distillation with
+    Semantic Calibration over every pair of feat_s[1:-1] x feat_t[1:-1]: distiller_zoo/SemCKD.py, the attention module SelfA trained
+    with the student in module_list[1], checkpointed under `self_attention` and resumed with it, the batch Gram matrices on
+    csrc/sp.hip and all pairs' weighted errors as one grouped call each way on csrc/semckd.hip; `-s / --soft` is the attention's
+    scale; a last batch shorter than --batch_size is skipped; the reference ships no launch line, the published one of SemCKD
+    is `--distill semckd -c 1 -d 1 -b 400`) and `crd` (Contrastive
     Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
     `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
     built -- the other comparison criteria are out of scope (SURVEY section 2);
@@ -55,7 +60,7 @@ from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
-from .distiller_zoo import PKT, Attention, ConvReg, DistillKL, HintLoss, NSTLoss, RKDLoss, Similarity, VIDLoss
+from .distiller_zoo import PKT, Attention, ConvReg, DistillKL, HintLoss, NSTLoss, RKDLoss, SelfA, SemCKDLoss, Similarity, VIDLoss
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
 from .learning.contrast_trainer import ContrastTrainer
@@ -261,6 +266,16 @@ def build_training(opt, device):
         regress_s = ConvReg(feat_s[opt.hint_layer].shape, feat_t[opt.hint_layer].shape)
         module_list.append(regress_s)
         trainable_list.append(regress_s)
+    elif opt.distill == "semckd":
+        # reference train_student_moma.py:358-364: the criterion is the weighted sum; SelfA (query / key heads for batches of
+        # opt.batch_size, one projection per pair of feat_s[1:-1] x feat_t[1:-1], its weights drawn here) trains with the student
+        # and rides in module_list[1]
+        s_n = [f.shape[1] for f in feat_s[1:-1]]
+        t_n = [f.shape[1] for f in feat_t[1:-1]]
+        criterion_kd = SemCKDLoss()
+        self_attention = SelfA(opt.batch_size, s_n, t_n, opt.soft)
+        module_list.append(self_attention)
+        trainable_list.append(self_attention)
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
@@ -395,7 +410,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         # criterion modules and the teacher are under no wrap: the reference relies on identical seeds; one flat
         # broadcast from rank 0 makes it a fact
         from .learning.ddp import broadcast_module_state
-        broadcast_module_state([criterion_list[2], model_t] + ([module_list[1]] if opt.distill == "hint" else []))
+        broadcast_module_state([criterion_list[2], model_t] + ([module_list[1]] if opt.distill in ("hint", "semckd") else []))
     if opt.amp == "fp16":
         opt._grad_scaler = torch.amp.GradScaler("cuda")
     print("opt.batch_size", opt.batch_size)
@@ -421,6 +436,8 @@ def main_worker(gpu, ngpus_per_node, opt):
         criterion_list[2].load_state_dict(ck["criterion_kd"])
         if opt.distill == "hint":
             module_list[1].load_state_dict(ck["regress_s"])             # (the trained regressor, before the optimizer state)
+        if opt.distill == "semckd":
+            module_list[1].load_state_dict(ck["self_attention"])        # (the trained SelfA, likewise)
         optimizer.load_state_dict(ck["optimizer"])
         if getattr(opt, "_grad_scaler", None) is not None and ck.get("grad_scaler"):
             opt._grad_scaler.load_state_dict(ck["grad_scaler"])         # (--amp fp16: the loss scale continues where it was)
@@ -443,7 +460,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         print("==> training...")
         t1 = time.time()
         train_acc, train_loss = train_distill_moma(epoch, train_loader, module_list, criterion_list,
-                                                   trainer if opt.distill in ("moma", "crd", "vid", "hint") else None, contrast, optimizer, opt)
+                                                   trainer if opt.distill in ("moma", "crd", "vid", "hint", "semckd") else None, contrast, optimizer, opt)
         if device.type == "cuda":
             torch.cuda.synchronize()
         t2 = time.time()
@@ -483,6 +500,7 @@ def main_worker(gpu, ngpus_per_node, opt):
             _atomic_save({"epoch": epoch, "model": model_s.state_dict(), "model_t": model_t.state_dict(),
                           "criterion_kd": criterion_list[2].state_dict(),
                           **({"regress_s": module_list[1].state_dict()} if opt.distill == "hint" else {}),
+                          **({"self_attention": module_list[1].state_dict()} if opt.distill == "semckd" else {}),
                           "contrast": contrast.state_dict() if contrast is not None else None,
                           "optimizer": optimizer.state_dict(), "best_acc": best_acc, "best_f1": best_f1,
                           "grad_scaler": opt._grad_scaler.state_dict() if getattr(opt, "_grad_scaler", None) is not None else None},
