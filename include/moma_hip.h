@@ -380,6 +380,47 @@ int moma_hint_bwd(const void* x, const void* t, const float* gamma, const float*
                   int layout_x, int dtype_t, int layout_t, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SRRL Softmax Regression Representation Learning (`--distill srrl`) on one pair of pooled features -- replaces what follows the
+ *      convolution in SRRL.forward (models/util.py: BatchNorm2d in training mode -> ReLU, then the TEACHER'S classifier on the result)
+ *      together with the two nn.MSELoss of train_student_moma.py:365-371 / helper/loops_moma.py:340-342 and their autograd backward.
+ *      For x (the convolution's output) and t (the teacher's feat[-1]), both [B, C], W [K, C] and bias [K] the teacher classifier's
+ *      Linear, logits [B, K] the teacher's, gamma and beta [C]:
+ *          mean_c = sum_b x / B     var_c = sum_b x^2 / B - mean_c^2   (biased; sums and variance in double)
+ *          invstd_c = 1 / sqrt(var_c + eps)       xh = (x - mean_c) invstd_c   (centred and scaled in double, rounded to fp32)
+ *          y = max(0, gamma_c xh + beta_c)        p = y W^T + bias     (fp32 FMA over 32 channels, those sums added in double; p
+ *                                                                       rounded once to fp32)
+ *          loss = sum (y - t)^2 / (B C) + sum (p - logits)^2 / (B K)
+ *          dY = 2 / (B C) (y - t) + 2 / (B K) (p - logits) W           g = dY [y > 0]   (strictly greater, as in torch)
+ *          A_c = sum_b g        B_c = sum_b g xh
+ *          d_beta_c = g_loss A_c     d_gamma_c = g_loss B_c     dx = g_loss gamma_c invstd_c (g - A_c / B - xh B_c / B)
+ *          running_mean_c <- (1 - momentum) running_mean_c + momentum mean_c
+ *          running_var_c  <- (1 - momentum) running_var_c  + momentum var_c B / (B - 1)
+ *      x, t, dx: MOMA_DT_F32 or MOMA_DT_BF16, chosen per side, rows contiguous and dense, aligned to their element size only (element
+ *      accesses of 32 neighbouring channels: no row length or base address is special); dx has x's dtype.  W, bias, logits, gamma,
+ *      beta, the running statistics, dxu, d_gamma, d_beta, loss and g_loss are fp32; sums (A [C] then B [C]) and the workspace are
+ *      double, 8-byte aligned.  Every sum over the batch is double.  No atomics: bitwise reproducible, independent of the grid.
+ *      t, logits, W and bias get no gradient (the classifier is the teacher's and constant).
+ *
+ * workspace      moma_srrl_workspace_bytes(B, C, K): mean, invstd, the per-channel and per-row squared errors, the split partial sums
+ *                of both products in double and p - logits [B, K] in fp32; written and read by moma_srrl_fwd alone.
+ * moma_srrl_fwd  -> loss [1], sums [2 C] and dxu [B, C] = dx for g_loss = 1 (everything is linear in g_loss, so the forward forms
+ *                the whole gradient and x, t, W, logits are not read again); running_mean / running_var / bias (each nullable);
+ *                y_out [B, C] and pred_out [B, K] (each nullable, fp32): y and p as the loss saw them.  Five launches.
+ * moma_srrl_bwd  dx (nullable) = round(dxu g_loss) in x's dtype; d_gamma, d_beta (each nullable) from sums.  One launch.  g_loss is a
+ *                DEVICE scalar (the upstream gradient of the loss, e.g. a GradScaler factor): nothing is read back to the host.
+ *      B < 2: MOMA_E_SHAPE (one value per channel has no variance; torch refuses likewise); B > MOMA_SRRL_MAX_B, C > MOMA_SRRL_MAX_C or
+ *      K > MOMA_SRRL_MAX_K: MOMA_E_UNSUPPORTED; unknown dtype: MOMA_E_DTYPE.  Nothing is launched in either case.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_SRRL_MAX_B = 1024, MOMA_SRRL_MAX_C = 4096, MOMA_SRRL_MAX_K = 1024 };
+size_t moma_srrl_workspace_bytes(int B, int C, int K);
+int moma_srrl_fwd(const void* x, const void* t, const float* W, const float* bias, const float* logits, const float* gamma,
+                  const float* beta, float* running_mean, float* running_var, float momentum, float eps, int B, int C, int K,
+                  int dtype_x, int dtype_t, void* workspace, size_t workspace_bytes, double* sums, float* dxu, float* loss,
+                  float* y_out, float* pred_out, moma_stream_t stream);
+int moma_srrl_bwd(const float* dxu, const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta, int B, int C,
+                  int dtype_x, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * RKDRelational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
  *      (distiller_zoo/RKD.py: pdist -> smooth L1 of the mean-normalised distances, and unsqueeze-difference -> F.normalize -> bmm ->
  *      smooth L1 of the angles) and its autograd backward to f_s, without any [B, B, D] temporary.  For f_s [B, Ds], f_t [B, Dt]

@@ -950,6 +950,50 @@ int moma_hint_bwd(const void* x, const void* t, const float* gamma, const float*
                                   dtype_t, layout_t, (hipStream_t)stream));
 }
 
+// ---- SRRL --------------------------------------------------------------------------------------------------------------------------
+static int srrl_check(int B, int C, int K) {
+    if (B <= 0 || C <= 0 || K <= 0) return MOMA_E_SHAPE;
+    if (B < 2) return MOMA_E_SHAPE;                                  // one value per channel has no variance
+    if (B > MOMA_SRRL_MAX_B || C > MOMA_SRRL_MAX_C || K > MOMA_SRRL_MAX_K) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_srrl_workspace_bytes(int B, int C, int K) {
+    if (srrl_check(B, C, K) != MOMA_OK) return 0;
+    return srrl_workspace_bytes(B, C, K);
+}
+
+int moma_srrl_fwd(const void* x, const void* t, const float* W, const float* bias, const float* logits, const float* gamma,
+                  const float* beta, float* running_mean, float* running_var, float momentum, float eps, int B, int C, int K,
+                  int dtype_x, int dtype_t, void* workspace, size_t workspace_bytes, double* sums, float* dxu, float* loss,
+                  float* y_out, float* pred_out, moma_stream_t stream) {
+    if (!x || !t || !W || !logits || !gamma || !beta || !workspace || !sums || !dxu || !loss) return MOMA_E_NULL;
+    const int rc = srrl_check(B, C, K);
+    if (rc != MOMA_OK) return rc;
+    if (bad_dt(dtype_x) || bad_dt(dtype_t)) return MOMA_E_DTYPE;
+    if (workspace_bytes < srrl_workspace_bytes(B, C, K)) return MOMA_E_WORKSPACE;
+    if (misaligned(x, dtype_x == MOMA_DT_BF16 ? 2 : 4) || misaligned(t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(W, 4) ||
+        misaligned(bias, 4) || misaligned(logits, 4) || misaligned(gamma, 4) || misaligned(beta, 4) || misaligned(running_mean, 4) ||
+        misaligned(running_var, 4) || misaligned(workspace, 8) || misaligned(sums, 8) || misaligned(dxu, 4) || misaligned(loss, 4) ||
+        misaligned(y_out, 4) || misaligned(pred_out, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_srrl_fwd(x, t, W, bias, logits, gamma, beta, running_mean, running_var, momentum, eps, B, C, K, dtype_x,
+                                  dtype_t, workspace, sums, dxu, loss, y_out, pred_out, (hipStream_t)stream));
+}
+
+int moma_srrl_bwd(const float* dxu, const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta, int B, int C,
+                  int dtype_x, moma_stream_t stream) {
+    if (!dxu || !sums || !g_loss) return MOMA_E_NULL;
+    if (!dx && !d_gamma && !d_beta) return MOMA_E_NULL;
+    const int rc = srrl_check(B, C, 1);
+    if (rc != MOMA_OK) return rc;
+    if (bad_dt(dtype_x)) return MOMA_E_DTYPE;
+    if (misaligned(dxu, 4) || misaligned(sums, 8) || misaligned(g_loss, 4) || misaligned(dx, dtype_x == MOMA_DT_BF16 ? 2 : 4) ||
+        misaligned(d_gamma, 4) || misaligned(d_beta, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_srrl_bwd(dxu, sums, g_loss, dx, d_gamma, d_beta, B, C, dtype_x, (hipStream_t)stream));
+}
+
 // ---- The losses on a B x B batch relation (rkd, sp, pkt): the guards they share ---------------------------------------------------
 // f [B, D] of `dtype` with lo <= B <= hi
 static int rel_check(int B, long long D, int dtype, int lo, int hi) {

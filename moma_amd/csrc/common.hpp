@@ -302,6 +302,15 @@ hipError_t launch_hint_bwd(const void* x, const void* t, const float* gamma, con
                            const double* invstd, const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta,
                            int B, int C, int P, int dt_x, int lay_x, int dt_t, int lay_t, hipStream_t st);
 
+// ---- srrl.hip (SRRL: training-mode BatchNorm, ReLU, the teacher's classifier and both squared errors behind the connector's convolution) --
+size_t srrl_workspace_bytes(int B, int C, int K);
+hipError_t launch_srrl_fwd(const void* x, const void* t, const float* W, const float* bias, const float* logits, const float* gamma,
+                           const float* beta, float* running_mean, float* running_var, float momentum, float eps, int B, int C, int K,
+                           int dt_x, int dt_t, void* workspace, double* sums, float* dxu, float* loss, float* y_out, float* pred_out,
+                           hipStream_t st);
+hipError_t launch_srrl_bwd(const float* dxu, const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta, int B,
+                           int C, int dt_x, hipStream_t st);
+
 // ---- rkd.hip (Relational Knowledge Distillation: pairwise squared distances, the distance and angle terms, the student's gradient) --
 size_t rkd_workspace_bytes(int B);
 hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st);

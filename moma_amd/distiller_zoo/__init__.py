@@ -6,7 +6,8 @@ from .PKT import PKT
 from .RKD import RKDLoss
 from .SemCKD import MLPEmbed, Proj, SelfA, SemCKDLoss
 from .SP import Similarity
+from .SRRL import SRRL
 from .VID import VIDLoss
 
-__all__ = ["Attention", "ConvReg", "DistillKL", "HintLoss", "MLPEmbed", "NSTLoss", "PKT", "Proj", "RKDLoss", "SelfA", "SemCKDLoss",
+__all__ = ["Attention", "ConvReg", "DistillKL", "HintLoss", "MLPEmbed", "NSTLoss", "PKT", "Proj", "RKDLoss", "SRRL", "SelfA", "SemCKDLoss",
            "Similarity", "VIDLoss"]

@@ -63,6 +63,18 @@ every pair's weighted error and its backward in ONE grouped call each on csrc/se
 built for one batch size: a shorter last batch is skipped before the step, as in the reference.  The module sits in the optimizer
 and in the checkpoint (key `self_attention`), and its gradients are synchronised across ranks with those of the other trainable
 criteria (the unused `regressor` of its MLPEmbed heads never gets a gradient: both exchanges skip such parameters).  The step is eager.
+
+`--distill srrl` (reference :180-182, :340-342): the KD term is criterion_kd(trans_feat_s, feat_t[-1]) + criterion_kd(pred_feat_s,
+logit_t) with (trans_feat_s, pred_feat_s) = module_list[1](feat_s[-1], cls_t) -- Softmax Regression Representation Learning:
+module_list[1] is the trained connector distiller_zoo.SRRL (bias-free 1 x 1 convolution -> BatchNorm -> ReLU), cls_t the teacher's
+own classifier (get_feat_modules()[-1]), criterion_kd a plain MSE.  The loop calls `module_list[1].loss(f_s, f_t, logit_t, cls_t)`,
+the same value in one piece: under the step's autocast the convolution is a GEMM and BatchNorm, ReLU, the classifier's product, both
+squared errors and their backward run on csrc/srrl.hip (the float64 composite on the CPU and in eval mode).  feat_t[-1] comes from the
+step's one teacher forward (graphed or not) and rides in the key slot as `rkd`'s does, the teacher's logits ride in fw["logit_t"].
+Every feat[-1] of shape [B, C, 1, ...] is taken as [B, C]: the reference's line :341 hands the 4-D feature of its backbones to a
+module that unsqueezes it twice and raises; :181 squeezes first.  The classifier gets no gradient.  The connector sits in the
+optimizer and in the checkpoint (key `model_fmsr`), and its gradients are synchronised across ranks with those of the other
+trainable criteria.  Validation is the student's own logits, unchanged.  No memory; the step is eager.
 """
 from __future__ import print_function
 
@@ -111,6 +123,7 @@ class MomaStep:
         self.model_s, self.model_t = module_list[0], module_list[-1]
         self.regress_s = module_list[1] if opt.distill == "hint" else None       # (--distill hint: the trained ConvReg)
         self.self_attention = module_list[1] if opt.distill == "semckd" else None  # (--distill semckd: the trained SelfA)
+        self.model_fmsr = module_list[1] if opt.distill == "srrl" else None        # (--distill srrl: the trained connector)
         self.trainer, self.contrast, self.optimizer, self.opt, self.dev = trainer, contrast, optimizer, opt, dev
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(getattr(opt, "amp", None))
         self.scaler = getattr(opt, "_grad_scaler", None)
@@ -167,7 +180,7 @@ class MomaStep:
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
             return lt.float(), ft[-1].float(), None
-        if opt.distill in ("rkd", "pkt"): # (:155-158 / :159-162) likewise, as autocast left it
+        if opt.distill in ("rkd", "pkt", "srrl"): # (:155-158 / :159-162 / :180-182) likewise, as autocast left it
             return lt.float(), ft[-1].detach(), None
         if opt.distill != "moma":
             return lt.float(), None, None
@@ -234,6 +247,9 @@ class MomaStep:
             f_s = feat_s[-1]                                                              # (:156)
         if opt.distill == "pkt":
             f_s = feat_s[-1]                                                              # (:160)
+        if opt.distill == "srrl":
+            f_s = feat_s[-1]                                                              # (:181)
+            out["logit_t"] = logit_t
         if opt.distill == "moma":
             with self.autocast():
                 f_s = criterion_kd.embed_s(feat_s[-1])                                    # (:323-324)
@@ -308,6 +324,10 @@ class MomaStep:
             return criterion_kd(fw["f_s"], fw["k"]).float()
         if opt.distill == "pkt":                                                          # (:159-162) likewise
             return criterion_kd(fw["f_s"], fw["k"]).float()
+        if opt.distill == "srrl":                                                         # (:180-182) connector + both MSEs as one value; f_t rides in fw["k"]
+            cls_t = _unwrap(self.model_t).get_feat_modules()[-1]
+            with self.autocast():                                                         # (the connector's convolution is a GEMM)
+                return self.model_fmsr.loss(fw["f_s"], fw["k"], fw["logit_t"], cls_t).float()
         if opt.distill != "moma":
             raise NotImplementedError(opt.distill)
         f_s, k, all_k, qp = fw["f_s"], fw["k"], fw["all_k"], fw["qp"]
@@ -365,7 +385,7 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
 
     criterion_kd = criterion_list[2]
     model_s, model_t = module_list[0], module_list[-1]
-    trained_kd = module_list[1] if opt.distill in ("hint", "semckd") else criterion_kd   # (hint, semckd: module_list[1] trains, the criterion has no state)
+    trained_kd = module_list[1] if opt.distill in ("hint", "semckd", "srrl") else criterion_kd   # (hint, semckd, srrl: module_list[1] trains, the criterion has no state)
 
     batch_time, losses, top1 = AverageMeter(), AverageMeter(), AverageMeter()
     n_batch = len(train_loader)
@@ -376,14 +396,14 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             if torch.cuda.is_available() else torch.device("cpu")
     step = MomaStep(module_list, criterion_list, trainer, contrast, optimizer, opt, dev)
     single_rank = bool(getattr(trainer, "grad_sync_single_rank", False))
-    sync_criterion = opt.distill in ("moma", "crd", "vid", "hint", "semckd") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
+    sync_criterion = opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
     flat_dp = isinstance(model_s, FlatDataParallel)
     flat_params = None
     if flat_dp:
         # learning/ddp.py: ONE flat all-reduce per step behind the backward -- the student's gradients and those of the trainable
         # criterion modules (atts_q / embed_s: not under any wrapper, un-synchronised in the reference)
         flat_params = model_s.grad_params()
-        if opt.distill in ("moma", "crd", "vid", "hint", "semckd"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
+        if opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
             flat_params = flat_params + [p for p in trained_kd.parameters() if p.requires_grad]
     elif sync_criterion:
         # stock DDP on the student: one flat all-reduce per step for the trainable criterion modules, launched from autograd

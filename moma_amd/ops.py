@@ -1689,6 +1689,117 @@ def hint_bn_relu_mse(x, target, weight, bias, running_mean, running_var, momentu
 
 
 # ------------------------------------------------------------------------------------------------
+# SRRL: training-mode BatchNorm -> ReLU -> MSE, the teacher's classifier -> MSE behind the connector's convolution   (models/util.py SRRL)
+# ------------------------------------------------------------------------------------------------
+def srrl_native(B: int, C: int, K: int, dtype=None) -> bool:
+    """Shapes (batch B, teacher channels C = t_n, classes K) whose tail behind the connector's convolution runs on csrc/srrl.hip; the
+    others take distiller_zoo.SRRL.composite.  The kernels serve 2 <= B <= 1024, 1 <= C <= 4096, 1 <= K <= 1024 (the C ABI's caps);
+    anything past them is refused here, so the module never asks the library for a shape it returns an error for.
+    By profiles/srrl_microbench.txt (B = 256; (C, K) in (1280, 4), (1280, 8), (1280, 1000), (256, 100), (2048, 1000), (768, 1000);
+    fp32 and bf16 storage; verdict: fused <= stock ops + the stock form's own spread; two series) all 12 rows hold in both series at
+    1.3 - 1.7 x (151 - 214 us against 234 - 308 us per forward + backward), so no measured row is turned away.  The rows that lost
+    did so on the first version of the GEMM kernel (32 x 32 tiles, no prefetch): (2048, 1000) at 298.8 against 257.8 us and 301.9
+    against 268.8 us in fp32, 292.5 against 254.9 us and 280.0 against 212.1 us in bf16; with the 64 x 64 tile they hold at 178.2 /
+    209.2 against 304.9 / 306.1 us (fp32) and 185.2 / 214.4 against 244.2 / 304.3 us (bf16).  `dtype` describes the convolution's
+    output; asked without it the table answers for the shape alone."""
+    if not (2 <= B <= _lib.SRRL_MAX_B and 1 <= C <= _lib.SRRL_MAX_C and 1 <= K <= _lib.SRRL_MAX_K):
+        return False
+    return True
+
+
+def _srrl_rows(f, name):
+    """-> dense [B, C] float32 / bfloat16 device tensor"""
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() != 2 or f.dtype not in _DT_CODES:
+        raise TypeError(f"srrl_bn_relu_dual_mse: {name} must be a 2-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+    if not f.is_contiguous():
+        raise ValueError(f"srrl_bn_relu_dual_mse: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is not contiguous")
+    return f
+
+
+class _SRRLTail(torch.autograd.Function):
+    """srrl_fwd (statistics, running statistics, both products, the loss, A, B and dx for an upstream gradient of 1) in the forward;
+    srrl_bwd (one launch: everything scaled by the upstream gradient) in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, target, cls_weight, cls_bias, logits, weight, bias, running_mean, running_var, momentum, eps):
+        lib = _lib.load()
+        _srrl_rows(x, "x")
+        _srrl_rows(target, "target")
+        B, Cc = x.shape
+        K = cls_weight.shape[0] if isinstance(cls_weight, torch.Tensor) and cls_weight.dim() == 2 else -1
+        for nm, v, shape in (("cls_weight", cls_weight, (K, Cc)), ("cls_bias", cls_bias, (K,)), ("logits", logits, (B, K)),
+                             ("weight", weight, (Cc,)), ("bias", bias, (Cc,)), ("running_mean", running_mean, (Cc,)),
+                             ("running_var", running_var, (Cc,))):
+            if v is None and nm in ("cls_bias", "running_mean", "running_var"):
+                continue
+            _dev(v, nm, torch.float32)
+            if tuple(v.shape) != shape:
+                raise ValueError(f"srrl_bn_relu_dual_mse: {nm} {tuple(v.shape)}, expected {shape}")
+        if tuple(target.shape) != (B, Cc):
+            raise ValueError(f"srrl_bn_relu_dual_mse: x {tuple(x.shape)} and target {tuple(target.shape)} do not agree")
+        if B < 2:
+            raise ValueError(f"srrl_bn_relu_dual_mse: expected more than 1 value per channel when training, got x {tuple(x.shape)}")
+        dev = x.device
+        codes = (_DT_CODES[x.dtype], _DT_CODES[target.dtype])
+        with _timed("moma_srrl_fwd"):
+            n = lib.moma_srrl_workspace_bytes(B, Cc, K)
+            if n == 0:
+                raise ValueError(f"srrl_bn_relu_dual_mse: x {tuple(x.shape)} with {K} classes is past the kernels' caps "
+                                 f"(B <= {_lib.SRRL_MAX_B}, C <= {_lib.SRRL_MAX_C}, K <= {_lib.SRRL_MAX_K})")
+            nd, nw = (B * Cc + 1) // 2, (n + 7) // 8
+            buf = torch.empty(2 * Cc + nd + nw, device=dev, dtype=torch.float64)    # (one allocation: A and B, dx for g = 1, workspace)
+            sums, dxu, ws = buf[:2 * Cc], buf[2 * Cc:2 * Cc + nd].view(torch.float32)[:B * Cc], buf[2 * Cc + nd:]
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            check(lib.moma_srrl_fwd(_ptr(x), _ptr(target), _ptr(cls_weight), _ptr(cls_bias), _ptr(logits), _ptr(weight), _ptr(bias),
+                                    _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), B, Cc, K, *codes, _ptr(ws),
+                                    nw * 8, _ptr(sums), _ptr(dxu), _ptr(loss), None, None, _stream()), "moma_srrl_fwd")
+        ctx.save_for_backward(sums, dxu, weight, bias)
+        ctx.x_meta = (B, Cc, x.dtype, codes[0])
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        sums, dxu, weight, bias = ctx.saved_tensors
+        B, Cc, dtype, code = ctx.x_meta
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        need = ctx.needs_input_grad
+        dx = d_w = d_b = None
+        if need[0] or need[5] or need[6]:
+            with _timed("moma_srrl_bwd"):
+                if need[0]:
+                    dx = torch.empty((B, Cc), device=dxu.device, dtype=dtype)
+                if need[5]:
+                    d_w = torch.empty_like(weight)
+                if need[6]:
+                    d_b = torch.empty_like(bias)
+                check(lib.moma_srrl_bwd(_ptr(dxu), _ptr(sums), _ptr(g), _ptr(dx), _ptr(d_w), _ptr(d_b), B, Cc, code, _stream()),
+                      "moma_srrl_bwd")
+        return dx, None, None, None, None, d_w, d_b, None, None, None, None
+
+
+def srrl_bn_relu_dual_mse(x, target, cls_weight, cls_bias, logits, weight, bias, running_mean, running_var, momentum, eps) -> torch.Tensor:
+    """SRRL behind the connector's convolution: with y = relu(batch_norm(x)) (training mode: batch statistics; running_mean /
+    running_var, each optional, updated in place with `momentum`, the variance unbiased),
+    mean((y - target)^2) + mean((y @ cls_weight.T + cls_bias - logits)^2).  x (the convolution's output) and target are [B, C],
+    float32 or bfloat16 independently per side and contiguous; cls_weight [K, C], cls_bias [K] (optional) -- the TEACHER'S classifier
+    -- , logits [B, K], weight, bias and the running statistics [C] are float32 -> scalar float32.  Gradients flow to x (in its
+    dtype), weight and bias; the target, the logits and the classifier get none."""
+    for t, nm in ((x, "x"), (target, "target"), (logits, "logits")):
+        _dev(t, nm, dtype=None, contiguous=False)
+    if x.dim() != 2 or target.dim() != 2:
+        raise ValueError(f"srrl_bn_relu_dual_mse: x and target must be [B, C], got {tuple(x.shape)} and {tuple(target.shape)}")
+    if torch.is_grad_enabled() and (target.requires_grad or logits.requires_grad):
+        raise ValueError("srrl_bn_relu_dual_mse: the kernels give no gradient to the target or the logits (detach them, or use "
+                         "distiller_zoo.SRRL.composite)")
+    if momentum is None:
+        raise ValueError("srrl_bn_relu_dual_mse: momentum=None (cumulative average) is served by distiller_zoo.SRRL.composite")
+    return _SRRLTail.apply(x, target, cls_weight, cls_bias, logits, weight, bias, running_mean, running_var, float(momentum), float(eps))
+
+
+# ------------------------------------------------------------------------------------------------
 # What the losses on a B x B batch relation (rkd, sp, pkt: below) share: guards, the [B, D] view, the backward call
 # ------------------------------------------------------------------------------------------------
 def _rel_side(op, f, name):

@@ -23,7 +23,13 @@ and launch lines carry over.  What differs:
     with the student in module_list[1], checkpointed under `self_attention` and resumed with it, the batch Gram matrices on
     csrc/sp.hip and all pairs' weighted errors as one grouped call each way on csrc/semckd.hip; `-s / --soft` is the attention's
     scale; a last batch shorter than --batch_size is skipped; the reference ships no launch line, the published one of SemCKD
-    is `--distill semckd -c 1 -d 1 -b 400`) and `crd` (Contrastive
+    is `--distill semckd -c 1 -d 1 -b 400`), `srrl` (Softmax Regression Representation Learning on the last feature:
+    distiller_zoo/SRRL.py, the connector -- bias-free 1 x 1 convolution, BatchNorm, ReLU -- trained with the student in
+    module_list[1], checkpointed under `model_fmsr` (the reference's variable name) and resumed with it, the convolution a plain
+    GEMM and everything behind it -- BatchNorm, ReLU, the teacher's classifier and both squared errors -- on the kernels of
+    csrc/srrl.hip; every feat[-1] of shape [B, C, 1, ...] is taken as [B, C], where the reference's moma loop raises on its own
+    backbones; the reference ships no launch line for it (none of its scripts names the criterion); SimKD's repository, which this
+    module's code descends from, is cited with `--distill srrl -c 1 -d 0 -b 1`, which could not be checked here) and `crd` (Contrastive
     Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
     `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
     built -- the other comparison criteria are out of scope (SURVEY section 2);
@@ -60,7 +66,8 @@ from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
-from .distiller_zoo import PKT, Attention, ConvReg, DistillKL, HintLoss, NSTLoss, RKDLoss, SelfA, SemCKDLoss, Similarity, VIDLoss
+from .distiller_zoo import (PKT, SRRL, Attention, ConvReg, DistillKL, HintLoss, NSTLoss, RKDLoss, SelfA, SemCKDLoss, Similarity,
+                            VIDLoss)
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
 from .learning.contrast_trainer import ContrastTrainer
@@ -276,6 +283,15 @@ def build_training(opt, device):
         self_attention = SelfA(opt.batch_size, s_n, t_n, opt.soft)
         module_list.append(self_attention)
         trainable_list.append(self_attention)
+    elif opt.distill == "srrl":
+        # reference train_student_moma.py:365-371: the criterion is a plain MSE (applied twice); the connector (bias-free 1 x 1
+        # convolution -> BatchNorm -> ReLU on feat_s[-1], its weights drawn here) trains with the student and rides in module_list[1]
+        s_n = feat_s[-1].shape[1]
+        t_n = feat_t[-1].shape[1]
+        model_fmsr = SRRL(s_n=s_n, t_n=t_n)
+        criterion_kd = nn.MSELoss()
+        module_list.append(model_fmsr)
+        trainable_list.append(model_fmsr)
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
@@ -410,7 +426,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         # criterion modules and the teacher are under no wrap: the reference relies on identical seeds; one flat
         # broadcast from rank 0 makes it a fact
         from .learning.ddp import broadcast_module_state
-        broadcast_module_state([criterion_list[2], model_t] + ([module_list[1]] if opt.distill in ("hint", "semckd") else []))
+        broadcast_module_state([criterion_list[2], model_t] + ([module_list[1]] if opt.distill in ("hint", "semckd", "srrl") else []))
     if opt.amp == "fp16":
         opt._grad_scaler = torch.amp.GradScaler("cuda")
     print("opt.batch_size", opt.batch_size)
@@ -438,6 +454,8 @@ def main_worker(gpu, ngpus_per_node, opt):
             module_list[1].load_state_dict(ck["regress_s"])             # (the trained regressor, before the optimizer state)
         if opt.distill == "semckd":
             module_list[1].load_state_dict(ck["self_attention"])        # (the trained SelfA, likewise)
+        if opt.distill == "srrl":
+            module_list[1].load_state_dict(ck["model_fmsr"])            # (the trained connector, likewise)
         optimizer.load_state_dict(ck["optimizer"])
         if getattr(opt, "_grad_scaler", None) is not None and ck.get("grad_scaler"):
             opt._grad_scaler.load_state_dict(ck["grad_scaler"])         # (--amp fp16: the loss scale continues where it was)
@@ -460,7 +478,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         print("==> training...")
         t1 = time.time()
         train_acc, train_loss = train_distill_moma(epoch, train_loader, module_list, criterion_list,
-                                                   trainer if opt.distill in ("moma", "crd", "vid", "hint", "semckd") else None, contrast, optimizer, opt)
+                                                   trainer if opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl") else None, contrast, optimizer, opt)
         if device.type == "cuda":
             torch.cuda.synchronize()
         t2 = time.time()
@@ -501,6 +519,7 @@ def main_worker(gpu, ngpus_per_node, opt):
                           "criterion_kd": criterion_list[2].state_dict(),
                           **({"regress_s": module_list[1].state_dict()} if opt.distill == "hint" else {}),
                           **({"self_attention": module_list[1].state_dict()} if opt.distill == "semckd" else {}),
+                          **({"model_fmsr": module_list[1].state_dict()} if opt.distill == "srrl" else {}),
                           "contrast": contrast.state_dict() if contrast is not None else None,
                           "optimizer": optimizer.state_dict(), "best_acc": best_acc, "best_f1": best_f1,
                           "grad_scaler": opt._grad_scaler.state_dict() if getattr(opt, "_grad_scaler", None) is not None else None},
