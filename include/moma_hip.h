@@ -421,6 +421,42 @@ int moma_srrl_bwd(const float* dxu, const double* sums, const float* g_loss, voi
                   int dtype_x, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CC   Correlation Congruence (`--distill correlation`) on one pair of flattened features -- replaces both LinearEmbed heads
+ *      (models/util.py: nn.Linear on each side's feat[-1]), Correlation.forward (distiller_zoo/CC.py: |f_s - f_t|, the product of
+ *      neighbouring rows, summed over the columns, averaged over the B - 1 pairs) and their autograd backward.  For x_s [B, Cs],
+ *      x_t [B, Ct] (the teacher's, constant), W_s [D, Cs], b_s [D], W_t [D, Ct], b_t [D]:
+ *          d = x_s W_s^T + b_s - (x_t W_t^T + b_t)      (products and sums in double: exact products; each side's total formed
+ *                                                        separately, subtracted, the bias difference added; d rounded ONCE to
+ *                                                        fp32)
+ *          delta = |d|     loss = sum_{i < B - 1} sum_k delta[i,k] delta[i+1,k] / (B - 1)     (down the rows of a column, in double)
+ *          G[i,k] = sign(d[i,k]) (delta[i-1,k] + delta[i+1,k]) / (B - 1)        (a missing neighbour counts 0; sign(0) = 0)
+ *          dx_s = g_loss G W_s     dW_s = g_loss G^T x_s     db_s = g_loss colsum(G)     dW_t = -g_loss G^T x_t     db_t = -db_s
+ *                                                       (fp32 FMA over 32 elements, those sums added in double)
+ *      x_s, x_t, dx_s: MOMA_DT_F32 or MOMA_DT_BF16, chosen per side, rows contiguous and dense, aligned to their element size only
+ *      (element accesses: no row length or base address is special); dx_s has x_s's dtype.  The weights, the biases, their gradients,
+ *      gu, d_out, loss and g_loss are fp32; the workspace is 8-byte aligned.  Every reduction total is double.  No atomics: bitwise
+ *      reproducible, independent of the allocation.  x_t gets no gradient.  BOTH heads are trained: W_t and b_t get theirs.
+ *
+ * workspace      moma_cc_workspace_bytes(B, Cs, Ct, D): the split partial sums of d and the columns' sums in double, d in fp32;
+ *                written and read by moma_cc_fwd alone.
+ * moma_cc_fwd    -> loss [1] and gu [B, D] = G (it does not depend on g_loss); d_out [B, D] (nullable, fp32): d as the loss saw it.
+ *                Three launches.
+ * moma_cc_bwd    ONE grouped launch over the output tiles of dx_s (needs W_s), dW_s (needs x_s), dW_t (needs x_t) and the bias sums;
+ *                every output is nullable (at least one must be asked for), an input is needed only by its output.  g_loss is a
+ *                DEVICE scalar, multiplied in double before the one rounding: a power of two scales every bit pattern exactly.
+ *                db_t is db_s with the sign bit flipped.
+ *      B < 2: MOMA_E_SHAPE (the reference's mean over an empty slice is NaN); B > MOMA_CC_MAX_B, Cs or Ct > MOMA_CC_MAX_C or
+ *      D > MOMA_CC_MAX_D: MOMA_E_UNSUPPORTED; unknown dtype: MOMA_E_DTYPE.  Nothing is launched in either case.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_CC_MAX_B = 1024, MOMA_CC_MAX_C = 4096, MOMA_CC_MAX_D = 4096 };
+size_t moma_cc_workspace_bytes(int B, int Cs, int Ct, int D);
+int moma_cc_fwd(const void* x_s, const void* x_t, const float* W_s, const float* b_s, const float* W_t, const float* b_t, int B, int Cs,
+                int Ct, int D, int dtype_s, int dtype_t, void* workspace, size_t workspace_bytes, float* gu, float* loss, float* d_out,
+                moma_stream_t stream);
+int moma_cc_bwd(const float* gu, const void* x_s, const void* x_t, const float* W_s, const float* g_loss, void* dx_s, float* dW_s,
+                float* db_s, float* dW_t, float* db_t, int B, int Cs, int Ct, int D, int dtype_s, int dtype_t, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * RKDRelational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
  *      (distiller_zoo/RKD.py: pdist -> smooth L1 of the mean-normalised distances, and unsqueeze-difference -> F.normalize -> bmm ->
  *      smooth L1 of the angles) and its autograd backward to f_s, without any [B, B, D] temporary.  For f_s [B, Ds], f_t [B, Dt]

@@ -994,6 +994,52 @@ int moma_srrl_bwd(const float* dxu, const double* sums, const float* g_loss, voi
     return hip_rc(launch_srrl_bwd(dxu, sums, g_loss, dx, d_gamma, d_beta, B, C, dtype_x, (hipStream_t)stream));
 }
 
+// ---- Correlation Congruence --------------------------------------------------------------------------------------------------------
+static int cc_check(int B, int Cs, int Ct, int D) {
+    if (B <= 0 || Cs <= 0 || Ct <= 0 || D <= 0) return MOMA_E_SHAPE;
+    if (B < 2) return MOMA_E_SHAPE;                                  // no pair of neighbouring rows: the reference's mean is NaN
+    if (B > MOMA_CC_MAX_B || Cs > MOMA_CC_MAX_C || Ct > MOMA_CC_MAX_C || D > MOMA_CC_MAX_D) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_cc_workspace_bytes(int B, int Cs, int Ct, int D) {
+    if (cc_check(B, Cs, Ct, D) != MOMA_OK) return 0;
+    return cc_workspace_bytes(B, Cs, Ct, D);
+}
+
+int moma_cc_fwd(const void* x_s, const void* x_t, const float* W_s, const float* b_s, const float* W_t, const float* b_t, int B, int Cs,
+                int Ct, int D, int dtype_s, int dtype_t, void* workspace, size_t workspace_bytes, float* gu, float* loss, float* d_out,
+                moma_stream_t stream) {
+    if (!x_s || !x_t || !W_s || !b_s || !W_t || !b_t || !workspace || !gu || !loss) return MOMA_E_NULL;
+    const int rc = cc_check(B, Cs, Ct, D);
+    if (rc != MOMA_OK) return rc;
+    if (bad_dt(dtype_s) || bad_dt(dtype_t)) return MOMA_E_DTYPE;
+    if (workspace_bytes < cc_workspace_bytes(B, Cs, Ct, D)) return MOMA_E_WORKSPACE;
+    if (misaligned(x_s, dtype_s == MOMA_DT_BF16 ? 2 : 4) || misaligned(x_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(W_s, 4) ||
+        misaligned(b_s, 4) || misaligned(W_t, 4) || misaligned(b_t, 4) || misaligned(workspace, 8) || misaligned(gu, 4) ||
+        misaligned(loss, 4) || misaligned(d_out, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_cc_fwd(x_s, x_t, W_s, b_s, W_t, b_t, B, Cs, Ct, D, dtype_s, dtype_t, workspace, gu, loss, d_out,
+                                (hipStream_t)stream));
+}
+
+int moma_cc_bwd(const float* gu, const void* x_s, const void* x_t, const float* W_s, const float* g_loss, void* dx_s, float* dW_s,
+                float* db_s, float* dW_t, float* db_t, int B, int Cs, int Ct, int D, int dtype_s, int dtype_t, moma_stream_t stream) {
+    if (!gu || !g_loss) return MOMA_E_NULL;
+    if (!dx_s && !dW_s && !db_s && !dW_t && !db_t) return MOMA_E_NULL;
+    if ((dx_s && !W_s) || (dW_s && !x_s) || (dW_t && !x_t)) return MOMA_E_NULL;      // an input is needed only by its output
+    const int rc = cc_check(B, Cs, Ct, D);
+    if (rc != MOMA_OK) return rc;
+    if (bad_dt(dtype_s) || bad_dt(dtype_t)) return MOMA_E_DTYPE;
+    const size_t es = dtype_s == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(gu, 4) || misaligned(x_s, es) || misaligned(x_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(W_s, 4) ||
+        misaligned(g_loss, 4) || misaligned(dx_s, es) || misaligned(dW_s, 4) || misaligned(db_s, 4) || misaligned(dW_t, 4) ||
+        misaligned(db_t, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_cc_bwd(gu, x_s, x_t, W_s, g_loss, dx_s, dW_s, db_s, dW_t, db_t, B, Cs, Ct, D, dtype_s, dtype_t,
+                                (hipStream_t)stream));
+}
+
 // ---- The losses on a B x B batch relation (rkd, sp, pkt): the guards they share ---------------------------------------------------
 // f [B, D] of `dtype` with lo <= B <= hi
 static int rel_check(int B, long long D, int dtype, int lo, int hi) {

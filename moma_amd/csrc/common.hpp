@@ -311,6 +311,14 @@ hipError_t launch_srrl_fwd(const void* x, const void* t, const float* W, const f
 hipError_t launch_srrl_bwd(const float* dxu, const double* sums, const float* g_loss, void* dx, float* d_gamma, float* d_beta, int B,
                            int C, int dt_x, hipStream_t st);
 
+// ---- cc.hip (Correlation Congruence: both LinearEmbed heads as one product, the neighbouring-row product of |difference|, every gradient) --
+size_t cc_workspace_bytes(int B, int Cs, int Ct, int D);
+hipError_t launch_cc_fwd(const void* x_s, const void* x_t, const float* W_s, const float* b_s, const float* W_t, const float* b_t, int B,
+                         int Cs, int Ct, int D, int dt_s, int dt_t, void* workspace, float* gu, float* loss, float* d_out,
+                         hipStream_t st);
+hipError_t launch_cc_bwd(const float* gu, const void* x_s, const void* x_t, const float* W_s, const float* g_loss, void* dx_s, float* dW_s,
+                         float* db_s, float* dW_t, float* db_t, int B, int Cs, int Ct, int D, int dt_s, int dt_t, hipStream_t st);
+
 // ---- rkd.hip (Relational Knowledge Distillation: pairwise squared distances, the distance and angle terms, the student's gradient) --
 size_t rkd_workspace_bytes(int B);
 hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st);

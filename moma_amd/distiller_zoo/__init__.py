@@ -1,4 +1,5 @@
 from .AT import Attention
+from .CC import Correlation, LinearEmbed
 from .FitNet import ConvReg, HintLoss
 from .KD import DistillKL
 from .NST import NSTLoss
@@ -9,5 +10,5 @@ from .SP import Similarity
 from .SRRL import SRRL
 from .VID import VIDLoss
 
-__all__ = ["Attention", "ConvReg", "DistillKL", "HintLoss", "MLPEmbed", "NSTLoss", "PKT", "Proj", "RKDLoss", "SRRL", "SelfA", "SemCKDLoss",
-           "Similarity", "VIDLoss"]
+__all__ = ["Attention", "ConvReg", "Correlation", "DistillKL", "HintLoss", "LinearEmbed", "MLPEmbed", "NSTLoss", "PKT", "Proj", "RKDLoss",
+           "SRRL", "SelfA", "SemCKDLoss", "Similarity", "VIDLoss"]

@@ -75,6 +75,15 @@ Every feat[-1] of shape [B, C, 1, ...] is taken as [B, C]: the reference's line 
 module that unsqueezes it twice and raises; :181 squeezes first.  The classifier gets no gradient.  The connector sits in the
 optimizer and in the checkpoint (key `model_fmsr`), and its gradients are synchronised across ranks with those of the other
 trainable criteria.  Validation is the student's own logits, unchanged.  No memory; the step is eager.
+
+`--distill correlation` (reference :168-171): the KD term is criterion_kd(module_list[1](feat_s[-1]), module_list[2](feat_t[-1])) --
+Correlation Congruence: module_list[1] and module_list[2] are the trained distiller_zoo.LinearEmbed heads of the student's and the
+teacher's side, criterion_kd the product of neighbouring rows of |f_s - f_t|.  The loop calls
+`criterion_kd.loss(module_list[1], module_list[2], f_s, f_t)`, the same value in one piece: both heads, the criterion and their backward
+run on csrc/cc.hip, which reads the heads' float32 weights whatever the step's autocast (the float64 composite on the CPU).
+feat_t[-1] comes from the step's one teacher forward (graphed or not) and rides detached in the key slot as `rkd`'s does, in the
+dtype autocast left it.  BOTH heads sit in the optimizer and in the checkpoint (keys `embed_s`, `embed_t`), and their gradients are
+synchronised across ranks with those of the other trainable criteria.  No memory; the step is eager.
 """
 from __future__ import print_function
 
@@ -124,6 +133,7 @@ class MomaStep:
         self.regress_s = module_list[1] if opt.distill == "hint" else None       # (--distill hint: the trained ConvReg)
         self.self_attention = module_list[1] if opt.distill == "semckd" else None  # (--distill semckd: the trained SelfA)
         self.model_fmsr = module_list[1] if opt.distill == "srrl" else None        # (--distill srrl: the trained connector)
+        self.embed_s, self.embed_t = (module_list[1], module_list[2]) if opt.distill == "correlation" else (None, None)   # (--distill correlation: both trained heads)
         self.trainer, self.contrast, self.optimizer, self.opt, self.dev = trainer, contrast, optimizer, opt, dev
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(getattr(opt, "amp", None))
         self.scaler = getattr(opt, "_grad_scaler", None)
@@ -180,7 +190,7 @@ class MomaStep:
             ft, lt = teacher(images, is_feat=True)
         if opt.distill == "crd":          # (:303-306) f_t = feat_t[-1] of this one forward rides in the key slot
             return lt.float(), ft[-1].float(), None
-        if opt.distill in ("rkd", "pkt", "srrl"): # (:155-158 / :159-162 / :180-182) likewise, as autocast left it
+        if opt.distill in ("rkd", "pkt", "srrl", "correlation"): # (:155-158 / :159-162 / :180-182 / :168-171) likewise, as autocast left it
             return lt.float(), ft[-1].detach(), None
         if opt.distill != "moma":
             return lt.float(), None, None
@@ -250,6 +260,8 @@ class MomaStep:
         if opt.distill == "srrl":
             f_s = feat_s[-1]                                                              # (:181)
             out["logit_t"] = logit_t
+        if opt.distill == "correlation":
+            f_s = feat_s[-1]                                                              # (:169)
         if opt.distill == "moma":
             with self.autocast():
                 f_s = criterion_kd.embed_s(feat_s[-1])                                    # (:323-324)
@@ -328,6 +340,9 @@ class MomaStep:
             cls_t = _unwrap(self.model_t).get_feat_modules()[-1]
             with self.autocast():                                                         # (the connector's convolution is a GEMM)
                 return self.model_fmsr.loss(fw["f_s"], fw["k"], fw["logit_t"], cls_t).float()
+        if opt.distill == "correlation":                                                  # (:168-171) both heads + the criterion as one value; f_t rides in fw["k"]
+            with self.autocast():
+                return criterion_kd.loss(self.embed_s, self.embed_t, fw["f_s"], fw["k"]).float()
         if opt.distill != "moma":
             raise NotImplementedError(opt.distill)
         f_s, k, all_k, qp = fw["f_s"], fw["k"], fw["all_k"], fw["qp"]
@@ -377,6 +392,18 @@ class MomaStep:
         return loss.detach(), (loss_kd.detach() if torch.is_tensor(loss_kd) else loss_kd), fw["acc"]
 
 
+def trained_kd_params(opt, module_list, criterion_kd):
+    """the parameters outside the student that train and whose gradients both exchanges carry: those of module_list[1] for hint, semckd
+    and srrl (the criterion has no state), of BOTH heads module_list[1] and module_list[2] for correlation, of the criterion otherwise"""
+    if opt.distill in ("hint", "semckd", "srrl"):
+        mods = [module_list[1]]
+    elif opt.distill == "correlation":
+        mods = [module_list[1], module_list[2]]
+    else:
+        mods = [criterion_kd]
+    return [p for m in mods for p in m.parameters() if p.requires_grad]
+
+
 def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer, contrast, optimizer, opt):
     """one epoch distillation; returns (top1.avg, losses.avg) like the reference."""
     for module in module_list:
@@ -385,7 +412,6 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
 
     criterion_kd = criterion_list[2]
     model_s, model_t = module_list[0], module_list[-1]
-    trained_kd = module_list[1] if opt.distill in ("hint", "semckd", "srrl") else criterion_kd   # (hint, semckd, srrl: module_list[1] trains, the criterion has no state)
 
     batch_time, losses, top1 = AverageMeter(), AverageMeter(), AverageMeter()
     n_batch = len(train_loader)
@@ -396,19 +422,19 @@ def train_distill_moma(epoch, train_loader, module_list, criterion_list, trainer
             if torch.cuda.is_available() else torch.device("cpu")
     step = MomaStep(module_list, criterion_list, trainer, contrast, optimizer, opt, dev)
     single_rank = bool(getattr(trainer, "grad_sync_single_rank", False))
-    sync_criterion = opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
+    sync_criterion = opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl", "correlation") and trainer is not None and (getattr(opt, "world_size", 1) > 1 or single_rank)
     flat_dp = isinstance(model_s, FlatDataParallel)
     flat_params = None
     if flat_dp:
         # learning/ddp.py: ONE flat all-reduce per step behind the backward -- the student's gradients and those of the trainable
         # criterion modules (atts_q / embed_s: not under any wrapper, un-synchronised in the reference)
         flat_params = model_s.grad_params()
-        if opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl"):     # (crd: embed_s AND embed_t train; the banks are buffers, per rank; vid: every pair's regressor and log_scale)
-            flat_params = flat_params + [p for p in trained_kd.parameters() if p.requires_grad]
+        if opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl", "correlation"):     # (crd, correlation: embed_s AND embed_t train; crd's banks are buffers, per rank; vid: every pair's regressor and log_scale)
+            flat_params = flat_params + trained_kd_params(opt, module_list, criterion_kd)
     elif sync_criterion:
         # stock DDP on the student: one flat all-reduce per step for the trainable criterion modules, launched from autograd
         # hooks (overlaps the backward)
-        trainer.attach_grad_sync([p for p in trained_kd.parameters() if p.requires_grad])
+        trainer.attach_grad_sync(trained_kd_params(opt, module_list, criterion_kd))
     # the teacher's two no-grad forwards per step are replayed from a HIP graph after a few eager calls
     # (opt.graph_teacher, default on for GPU runs; see helper/graphs.py); everything else uses `model_t` itself
     teacher = model_t

@@ -1800,6 +1800,113 @@ def srrl_bn_relu_dual_mse(x, target, cls_weight, cls_bias, logits, weight, bias,
 
 
 # ------------------------------------------------------------------------------------------------
+# Correlation Congruence: both LinearEmbed heads, |difference|, the neighbouring-row product and every gradient   (distiller_zoo/CC.py)
+# ------------------------------------------------------------------------------------------------
+def cc_native(B: int, Cs: int, Ct: int, D: int, dtype=None) -> bool:
+    """Shapes (batch B, student width Cs, teacher width Ct, embedding width D = --feat_dim) whose two heads and criterion run on
+    csrc/cc.hip; the others take distiller_zoo.Correlation.composite.  The kernels serve 2 <= B <= 1024, 1 <= Cs, Ct <= 4096,
+    1 <= D <= 4096 (the C ABI's caps); anything past them is refused here, so the module never asks the library for a shape it returns
+    an error for.  By profiles/cc_microbench.txt (B in (64, 256); widths 256, 768, 1280, 2048 on both sides; D in (128, 512); fp32 and
+    bf16 storage -- the two series; verdict: fused <= stock ops + the stock form's own spread) all 32 rows hold at 1.4 - 3.7 x
+    (90 - 258 us against 268 - 398 us per forward + backward), so no measured shape class is turned away.  The rows that came
+    nearest did so on the first version of the finalize kernel (16 columns per workgroup): (256, 2048, 2048, 128) at 294.6 against
+    358.9 us in fp32 and 281.4 against 289.7 us in bf16; with 4 columns per workgroup they hold at 161.8 against 268.6 us and 204.6
+    against 350.1 us.  `dtype` describes x_s; asked without it the table answers for the shape alone."""
+    if not (2 <= B <= _lib.CC_MAX_B and 1 <= Cs <= _lib.CC_MAX_C and 1 <= Ct <= _lib.CC_MAX_C and 1 <= D <= _lib.CC_MAX_D):
+        return False
+    return True
+
+
+def _cc_rows(f, name):
+    """-> dense [B, C] float32 / bfloat16 device tensor"""
+    _dev(f, name, dtype=None, contiguous=False)
+    if f.dim() != 2 or f.dtype not in _DT_CODES:
+        raise TypeError(f"cc_embed_neighbour: {name} must be a 2-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+    if not f.is_contiguous():
+        raise ValueError(f"cc_embed_neighbour: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is not contiguous")
+    return f
+
+
+class _CCEmbedNeighbour(torch.autograd.Function):
+    """cc_fwd (the difference of both heads, the loss, G = d loss / d difference) in the forward; cc_bwd (one grouped launch: the three
+    products on G and the bias sums, scaled by the upstream gradient) in the backward."""
+
+    @staticmethod
+    def forward(ctx, x_s, x_t, w_s, b_s, w_t, b_t):
+        lib = _lib.load()
+        _cc_rows(x_s, "x_s")
+        _cc_rows(x_t, "x_t")
+        B, Cs = x_s.shape
+        Ct = x_t.shape[1]
+        D = w_s.shape[0] if isinstance(w_s, torch.Tensor) and w_s.dim() == 2 else -1
+        for nm, v, shape in (("w_s", w_s, (D, Cs)), ("b_s", b_s, (D,)), ("w_t", w_t, (D, Ct)), ("b_t", b_t, (D,))):
+            _dev(v, nm, torch.float32)
+            if tuple(v.shape) != shape:
+                raise ValueError(f"cc_embed_neighbour: {nm} {tuple(v.shape)}, expected {shape}")
+        if x_t.shape[0] != B:
+            raise ValueError(f"cc_embed_neighbour: x_s {tuple(x_s.shape)} and x_t {tuple(x_t.shape)} do not agree in the batch")
+        if B < 2:
+            raise ValueError(f"cc_embed_neighbour: no pair of neighbouring rows in x_s {tuple(x_s.shape)} (the reference's mean over an "
+                             "empty slice is NaN: distiller_zoo.Correlation.composite)")
+        dev = x_s.device
+        codes = (_DT_CODES[x_s.dtype], _DT_CODES[x_t.dtype])
+        with _timed("moma_cc_fwd"):
+            n = lib.moma_cc_workspace_bytes(B, Cs, Ct, D)
+            if n == 0:
+                raise ValueError(f"cc_embed_neighbour: x_s {tuple(x_s.shape)}, x_t {tuple(x_t.shape)} with {D} outputs is past the kernels' "
+                                 f"caps (B <= {_lib.CC_MAX_B}, Cs, Ct <= {_lib.CC_MAX_C}, D <= {_lib.CC_MAX_D})")
+            nw = (n + 7) // 8
+            ws = torch.empty(nw, device=dev, dtype=torch.float64)
+            gu = torch.empty((B, D), device=dev, dtype=torch.float32)
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            check(lib.moma_cc_fwd(_ptr(x_s), _ptr(x_t), _ptr(w_s), _ptr(b_s), _ptr(w_t), _ptr(b_t), B, Cs, Ct, D, *codes, _ptr(ws), nw * 8,
+                                  _ptr(gu), _ptr(loss), None, _stream()), "moma_cc_fwd")
+        ctx.save_for_backward(gu, x_s, x_t, w_s)
+        ctx.meta = (B, Cs, Ct, D, codes)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        gu, x_s, x_t, w_s = ctx.saved_tensors
+        B, Cs, Ct, D, codes = ctx.meta
+        g = g.to(torch.float32).contiguous()          # the upstream gradient stays on the device (a GradScaler factor rides in it)
+        need = ctx.needs_input_grad
+        dx = dws = dbs = dwt = dbt = None
+        if need[0] or need[2] or need[3] or need[4] or need[5]:
+            with _timed("moma_cc_bwd"):
+                dev = gu.device
+                if need[0]:
+                    dx = torch.empty((B, Cs), device=dev, dtype=x_s.dtype)
+                if need[2]:
+                    dws = torch.empty((D, Cs), device=dev, dtype=torch.float32)
+                if need[3]:
+                    dbs = torch.empty((D,), device=dev, dtype=torch.float32)
+                if need[4]:
+                    dwt = torch.empty((D, Ct), device=dev, dtype=torch.float32)
+                if need[5]:
+                    dbt = torch.empty((D,), device=dev, dtype=torch.float32)
+                check(lib.moma_cc_bwd(_ptr(gu), _ptr(x_s), _ptr(x_t), _ptr(w_s), _ptr(g), _ptr(dx), _ptr(dws), _ptr(dbs), _ptr(dwt),
+                                      _ptr(dbt), B, Cs, Ct, D, *codes, _stream()), "moma_cc_bwd")
+        return dx, None, dws, dbs, dwt, dbt
+
+
+def cc_embed_neighbour(x_s, x_t, w_s, b_s, w_t, b_t) -> torch.Tensor:
+    """Correlation Congruence behind both backbones: with d = x_s @ w_s.T + b_s - (x_t @ w_t.T + b_t),
+    mean over the B - 1 pairs of neighbouring rows of sum_k |d[i, k]| |d[i + 1, k]|.  x_s [B, Cs] and x_t [B, Ct] are float32 or
+    bfloat16 independently per side and contiguous; w_s [D, Cs], b_s [D], w_t [D, Ct], b_t [D] are float32 -> scalar float32.
+    Gradients flow to x_s (in its dtype) and to BOTH heads' weights and biases; x_t gets none."""
+    for t, nm in ((x_s, "x_s"), (x_t, "x_t")):
+        _dev(t, nm, dtype=None, contiguous=False)
+    if x_s.dim() != 2 or x_t.dim() != 2:
+        raise ValueError(f"cc_embed_neighbour: x_s and x_t must be [B, C], got {tuple(x_s.shape)} and {tuple(x_t.shape)}")
+    if torch.is_grad_enabled() and x_t.requires_grad:
+        raise ValueError("cc_embed_neighbour: the kernels give no gradient to x_t (detach it, or use distiller_zoo.Correlation.composite)")
+    return _CCEmbedNeighbour.apply(x_s, x_t, w_s, b_s, w_t, b_t)
+
+
+# ------------------------------------------------------------------------------------------------
 # What the losses on a B x B batch relation (rkd, sp, pkt: below) share: guards, the [B, D] view, the backward call
 # ------------------------------------------------------------------------------------------------
 def _rel_side(op, f, name):

@@ -29,7 +29,11 @@ and launch lines carry over.  What differs:
     GEMM and everything behind it -- BatchNorm, ReLU, the teacher's classifier and both squared errors -- on the kernels of
     csrc/srrl.hip; every feat[-1] of shape [B, C, 1, ...] is taken as [B, C], where the reference's moma loop raises on its own
     backbones; the reference ships no launch line for it (none of its scripts names the criterion); SimKD's repository, which this
-    module's code descends from, is cited with `--distill srrl -c 1 -d 0 -b 1`, which could not be checked here) and `crd` (Contrastive
+    module's code descends from, is cited with `--distill srrl -c 1 -d 0 -b 1`, which could not be checked here), `correlation`
+    (Correlation Congruence on the last feature: distiller_zoo/CC.py, one LinearEmbed head of --feat_dim outputs per side, BOTH
+    trained with the student in module_list[1] and module_list[2], checkpointed under `embed_s` and `embed_t` and resumed with it,
+    both heads, the criterion and their backward on the kernels of csrc/cc.hip; the reference's launch line is
+    `--distill correlation -c 1 -d 1 -b 0.02`) and `crd` (Contrastive
     Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
     `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
     built -- the other comparison criteria are out of scope (SURVEY section 2);
@@ -66,8 +70,8 @@ from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
-from .distiller_zoo import (PKT, SRRL, Attention, ConvReg, DistillKL, HintLoss, NSTLoss, RKDLoss, SelfA, SemCKDLoss, Similarity,
-                            VIDLoss)
+from .distiller_zoo import (PKT, SRRL, Attention, ConvReg, Correlation, DistillKL, HintLoss, LinearEmbed, NSTLoss, RKDLoss, SelfA,
+                            SemCKDLoss, Similarity, VIDLoss)
 from .helper.loops_moma import macro_f1, train_distill_moma, validate_distill
 from .helper.util import adjust_learning_rate, reduce_tensor, save_dict_to_json, update_dict_to_json
 from .learning.contrast_trainer import ContrastTrainer
@@ -292,6 +296,16 @@ def build_training(opt, device):
         criterion_kd = nn.MSELoss()
         module_list.append(model_fmsr)
         trainable_list.append(model_fmsr)
+    elif opt.distill == "correlation":
+        # reference train_student_comparison.py:388-395: the criterion has no state; one LinearEmbed per side on feat[-1] (the
+        # student's drawn first, then the teacher's) and BOTH train: they ride in module_list[1] and module_list[2]
+        criterion_kd = Correlation()
+        embed_s = LinearEmbed(feat_s[-1].shape[1], opt.feat_dim)
+        embed_t = LinearEmbed(feat_t[-1].shape[1], opt.feat_dim)
+        module_list.append(embed_s)
+        module_list.append(embed_t)
+        trainable_list.append(embed_s)
+        trainable_list.append(embed_t)
     else:
         raise NotImplementedError(opt.distill)
     criterion_list = nn.ModuleList([criterion_cls, criterion_div, criterion_kd])
@@ -335,6 +349,21 @@ def make_optimizer(params, opt, device, fused=None):
                 torch.autograd.graph.increment_version(ps)
         optimizer.register_step_post_hook(_advance_versions)
     return optimizer
+
+
+# the trained modules that ride in module_list behind the student (none for the other criteria), under their checkpoint keys
+AUX_MODULE_KEYS = {"hint": ("regress_s",), "semckd": ("self_attention",), "srrl": ("model_fmsr",), "correlation": ("embed_s", "embed_t")}
+
+
+def aux_modules(opt, module_list):
+    """[(checkpoint key, module)] of the trained modules between the student and the teacher in module_list"""
+    keys = AUX_MODULE_KEYS.get(opt.distill, ())
+    return [(k, module_list[1 + i]) for i, k in enumerate(keys)]
+
+
+def broadcast_list(opt, module_list, criterion_list, model_t):
+    """what rank 0 hands to the other ranks at start-up: the criterion, the teacher and every trained module behind the student"""
+    return [criterion_list[2], model_t] + [m for _k, m in aux_modules(opt, module_list)]
 
 
 def _rank_state_path(folder, rank):
@@ -426,7 +455,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         # criterion modules and the teacher are under no wrap: the reference relies on identical seeds; one flat
         # broadcast from rank 0 makes it a fact
         from .learning.ddp import broadcast_module_state
-        broadcast_module_state([criterion_list[2], model_t] + ([module_list[1]] if opt.distill in ("hint", "semckd", "srrl") else []))
+        broadcast_module_state(broadcast_list(opt, module_list, criterion_list, model_t))
     if opt.amp == "fp16":
         opt._grad_scaler = torch.amp.GradScaler("cuda")
     print("opt.batch_size", opt.batch_size)
@@ -450,12 +479,8 @@ def main_worker(gpu, ngpus_per_node, opt):
         model_s.load_state_dict(ck["model"])
         model_t.load_state_dict(ck["model_t"])
         criterion_list[2].load_state_dict(ck["criterion_kd"])
-        if opt.distill == "hint":
-            module_list[1].load_state_dict(ck["regress_s"])             # (the trained regressor, before the optimizer state)
-        if opt.distill == "semckd":
-            module_list[1].load_state_dict(ck["self_attention"])        # (the trained SelfA, likewise)
-        if opt.distill == "srrl":
-            module_list[1].load_state_dict(ck["model_fmsr"])            # (the trained connector, likewise)
+        for key, mod in aux_modules(opt, module_list):                  # (hint: the trained regressor; semckd: SelfA; srrl: the connector;
+            mod.load_state_dict(ck[key])                                #  correlation: both heads -- before the optimizer state)
         optimizer.load_state_dict(ck["optimizer"])
         if getattr(opt, "_grad_scaler", None) is not None and ck.get("grad_scaler"):
             opt._grad_scaler.load_state_dict(ck["grad_scaler"])         # (--amp fp16: the loss scale continues where it was)
@@ -478,7 +503,7 @@ def main_worker(gpu, ngpus_per_node, opt):
         print("==> training...")
         t1 = time.time()
         train_acc, train_loss = train_distill_moma(epoch, train_loader, module_list, criterion_list,
-                                                   trainer if opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl") else None, contrast, optimizer, opt)
+                                                   trainer if opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl", "correlation") else None, contrast, optimizer, opt)
         if device.type == "cuda":
             torch.cuda.synchronize()
         t2 = time.time()
@@ -517,9 +542,7 @@ def main_worker(gpu, ngpus_per_node, opt):
             # full training state (the reference saves the student only): shared part by the main rank ...
             _atomic_save({"epoch": epoch, "model": model_s.state_dict(), "model_t": model_t.state_dict(),
                           "criterion_kd": criterion_list[2].state_dict(),
-                          **({"regress_s": module_list[1].state_dict()} if opt.distill == "hint" else {}),
-                          **({"self_attention": module_list[1].state_dict()} if opt.distill == "semckd" else {}),
-                          **({"model_fmsr": module_list[1].state_dict()} if opt.distill == "srrl" else {}),
+                          **{key: mod.state_dict() for key, mod in aux_modules(opt, module_list)},
                           "contrast": contrast.state_dict() if contrast is not None else None,
                           "optimizer": optimizer.state_dict(), "best_acc": best_acc, "best_f1": best_f1,
                           "grad_scaler": opt._grad_scaler.state_dict() if getattr(opt, "_grad_scaler", None) is not None else None},
