@@ -457,6 +457,42 @@ int moma_cc_bwd(const float* gu, const void* x_s, const void* x_t, const float* 
                 float* db_s, float* dW_t, float* db_t, int B, int Cs, int Ct, int D, int dtype_s, int dtype_t, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CE   The classification head of the teacher trainer (`train_teacher.py`) -- replaces nn.CrossEntropyLoss (mean over the rows,
+ *      ignore_index -100), helper/util.accuracy (top-1) and, in validation, the argmax and confusion matrix of
+ *      process_accumulated_output, with their autograd backward.  For logits z [B, K] and labels y [B]:
+ *          m_b = max_k z[b,k]     pred_b = the LOWEST k with z[b,k] = m_b     lse_b = m_b + log1p(sum_{k != pred_b} exp(z[b,k] - m_b))
+ *          row_b = lse_b - z[b,y_b] (formed as log1p(..) + (m_b - z[b,y_b]))  for a VALID row, 0 <= y_b < K
+ *          loss = sum_valid row_b / n_valid                                   (n_valid = 0: NaN, as nn.CrossEntropyLoss)
+ *          dz[b,k] = g_loss (exp(z[b,k] - lse_b) - [k == y_b]) / n_valid      (a row that is not valid: exact zeros)
+ *      Every sum, exponential and logarithm is double; lse and 1 / n_valid are kept in double.
+ *      z, dz: MOMA_DT_F32 or MOMA_DT_BF16, rows contiguous and dense, aligned to their element size (16-byte or 4-element accesses
+ *      where the base address and K allow, element accesses otherwise: K = 5 is as legal as K = 8); dz has z's dtype.  labels: int64.
+ *      A label of -100 is ignored: no loss, left out of the mean, no gradient, never a hit, nothing in conf.  ANY OTHER label outside
+ *      [0, K) is never used as an index: it makes loss NaN, its row of dz zero, and is counted in stats[3] (stock torch answers it
+ *      with a device-side assert that ends the process: a deliberate deviation).
+ *
+ * workspace      moma_ce_workspace_bytes(B, K) (8-byte aligned): the rows' losses, predictions and flags between the two launches.
+ * moma_ce_fwd    -> loss [1] fp32; lse [B] and inv_n [1] = 1 / n_valid, double, for moma_ce_bwd; and, each nullable:
+ *                pred [B] int32; stats [4] double, to which it ADDS (sum of the valid rows' losses, hits, valid rows, rows with a bad
+ *                label); conf [K, K] int64 (row = label, column = prediction), to which it adds 1 at [y_b, pred_b] per valid row.
+ *                Two launches: the rows (G lanes per row, G the power of two in 1 .. 64 that covers ceil(K / 16); rows of up to
+ *                MOMA_CE_ONE_WALK_K elements are read once, longer ones twice), then ONE workgroup that adds the rows' losses in row
+ *                order (256 consecutive runs of rows, their sums in order) and rounds loss once.  conf takes integer atomics (exact);
+ *                no floating-point total does: bitwise reproducible, independent of the allocation (the access width follows the
+ *                base address's alignment, and with it the last bits of lse).  Nothing happens on the host but the argument checks.
+ * moma_ce_bwd    -> dz.  One launch, no reduction.  g_loss is a DEVICE scalar (fp32), multiplied in double before the one rounding:
+ *                a power of two scales every bit pattern exactly.
+ *      B < 1 or K < 1: MOMA_E_SHAPE; unknown dtype: MOMA_E_DTYPE; B > MOMA_CE_MAX_B or K > MOMA_CE_MAX_K: MOMA_E_UNSUPPORTED (the
+ *      caps keep every element index, B K and K K, below 2^31).  Nothing is launched and nothing written in any of these cases.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_CE_MAX_B = 16384, MOMA_CE_MAX_K = 32768, MOMA_CE_ONE_WALK_K = 1024 };
+size_t moma_ce_workspace_bytes(int B, int K);
+int moma_ce_fwd(const void* z, const int64_t* labels, int B, int K, int dtype, void* workspace, size_t workspace_bytes, float* loss,
+                double* lse, double* inv_n, int32_t* pred, double* stats, int64_t* conf, moma_stream_t stream);
+int moma_ce_bwd(const void* z, const int64_t* labels, const double* lse, const double* inv_n, const float* g_loss, void* dz, int B,
+                int K, int dtype, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * RKDRelational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
  *      (distiller_zoo/RKD.py: pdist -> smooth L1 of the mean-normalised distances, and unsqueeze-difference -> F.normalize -> bmm ->
  *      smooth L1 of the angles) and its autograd backward to f_s, without any [B, B, D] temporary.  For f_s [B, Ds], f_t [B, Dt]

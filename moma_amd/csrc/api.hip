@@ -1040,6 +1040,43 @@ int moma_cc_bwd(const float* gu, const void* x_s, const void* x_t, const float* 
                                 (hipStream_t)stream));
 }
 
+// ---- The classification head (cross-entropy, top-1, confusion matrix) ---------------------------------------------------------------
+static int ce_check(int B, int K, int dtype) {
+    if (B < 1 || K < 1) return MOMA_E_SHAPE;
+    if (bad_dt(dtype)) return MOMA_E_DTYPE;
+    if (B > MOMA_CE_MAX_B || K > MOMA_CE_MAX_K) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_ce_workspace_bytes(int B, int K) {
+    if (ce_check(B, K, MOMA_DT_F32) != MOMA_OK) return 0;
+    return ce_workspace_bytes(B);
+}
+
+int moma_ce_fwd(const void* z, const int64_t* labels, int B, int K, int dtype, void* workspace, size_t workspace_bytes, float* loss,
+                double* lse, double* inv_n, int32_t* pred, double* stats, int64_t* conf, moma_stream_t stream) {
+    if (!z || !labels || !workspace || !loss || !lse || !inv_n) return MOMA_E_NULL;
+    const int rc = ce_check(B, K, dtype);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < ce_workspace_bytes(B)) return MOMA_E_WORKSPACE;
+    if (misaligned(z, dtype == MOMA_DT_BF16 ? 2 : 4) || misaligned(labels, 8) || misaligned(workspace, 8) || misaligned(loss, 4) ||
+        misaligned(lse, 8) || misaligned(inv_n, 8) || misaligned(pred, 4) || misaligned(stats, 8) || misaligned(conf, 8))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_ce_fwd(z, labels, B, K, dtype, workspace, loss, lse, inv_n, pred, stats, conf, (hipStream_t)stream));
+}
+
+int moma_ce_bwd(const void* z, const int64_t* labels, const double* lse, const double* inv_n, const float* g_loss, void* dz, int B,
+                int K, int dtype, moma_stream_t stream) {
+    if (!z || !labels || !lse || !inv_n || !g_loss || !dz) return MOMA_E_NULL;
+    const int rc = ce_check(B, K, dtype);
+    if (rc != MOMA_OK) return rc;
+    const size_t eb = dtype == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(z, eb) || misaligned(dz, eb) || misaligned(labels, 8) || misaligned(lse, 8) || misaligned(inv_n, 8) ||
+        misaligned(g_loss, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_ce_bwd(z, labels, lse, inv_n, g_loss, dz, B, K, dtype, (hipStream_t)stream));
+}
+
 // ---- The losses on a B x B batch relation (rkd, sp, pkt): the guards they share ---------------------------------------------------
 // f [B, D] of `dtype` with lo <= B <= hi
 static int rel_check(int B, long long D, int dtype, int lo, int hi) {

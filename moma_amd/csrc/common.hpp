@@ -319,6 +319,13 @@ hipError_t launch_cc_fwd(const void* x_s, const void* x_t, const float* W_s, con
 hipError_t launch_cc_bwd(const float* gu, const void* x_s, const void* x_t, const float* W_s, const float* g_loss, void* dx_s, float* dW_s,
                          float* db_s, float* dW_t, float* db_t, int B, int Cs, int Ct, int D, int dt_s, int dt_t, hipStream_t st);
 
+// ---- ce.hip (the teacher trainer's classification head: cross-entropy, top-1 and the confusion matrix, the logits' gradient) ----------
+size_t ce_workspace_bytes(int B);
+hipError_t launch_ce_fwd(const void* z, const int64_t* labels, int B, int K, int dtype, void* workspace, float* loss, double* lse,
+                         double* inv_n, int32_t* pred, double* stats, int64_t* conf, hipStream_t st);
+hipError_t launch_ce_bwd(const void* z, const int64_t* labels, const double* lse, const double* inv_n, const float* g_loss, void* dz,
+                         int B, int K, int dtype, hipStream_t st);
+
 // ---- rkd.hip (Relational Knowledge Distillation: pairwise squared distances, the distance and angle terms, the student's gradient) --
 size_t rkd_workspace_bytes(int B);
 hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st);

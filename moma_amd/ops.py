@@ -1907,6 +1907,108 @@ def cc_embed_neighbour(x_s, x_t, w_s, b_s, w_t, b_t) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# The classification head of the teacher trainer: cross-entropy, top-1 and the confusion matrix   (helper/loops_moma.py:13-65, :376-444)
+# ------------------------------------------------------------------------------------------------
+def ce_native(B: int, K: int, dtype=None) -> bool:
+    """Shapes (batch B, classes K) whose cross-entropy, top-1 count and confusion matrix run on csrc/ce.hip; the others take
+    helper.ce_head.CrossEntropyHead.composite.  The kernels serve 1 <= B <= 16384 and 1 <= K <= 32768 (the C ABI's caps); anything
+    past them is refused here, so the module never asks the library for a shape it returns an error for.  By
+    profiles/ce_microbench.txt (B in (64, 256) x K in (4, 9, 100, 1000), fp32 and bf16 logits, the training and the validation
+    series; verdict: fused <= stock ops + the stock form's own spread in BOTH series) all 8 bf16 rows hold (training 1.03 - 1.64 x,
+    validation 4.6 - 6.0 x), and 7 of the 8 fp32 rows LOSE their training series: 127 - 139 us against 119 - 129 us per forward +
+    backward, although the same rows win validation 3.5 - 6.0 x and the three launches take 25 - 30 us.  The loss is host time: the
+    stock chain on fp32 logits has no casts (11 launches against 13 for bf16) and a backward made of C++ nodes, while the fused
+    backward is a Python node that the autograd thread must take the interpreter lock for.  That class -- fp32 logits, every shape --
+    goes to the composite; bf16 logits, what `--amp bf16` hands the head, stay on the kernels.  `dtype` describes the logits; asked
+    without it the table answers for the shape alone."""
+    if not (1 <= B <= _lib.CE_MAX_B and 1 <= K <= _lib.CE_MAX_K):
+        return False
+    if dtype == torch.float32:
+        return False
+    return True
+
+
+class _CEHead(torch.autograd.Function):
+    """ce_fwd (the loss, lse and 1 / n_valid; the meter's sums and the confusion matrix where asked for) in the forward; ce_bwd (one
+    launch, no reduction) in the backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, stats, conf):
+        lib = _lib.load()
+        B, K = logits.shape
+        dev = logits.device
+        code = _DT_CODES[logits.dtype]
+        ctx.set_materialize_grads(False)
+        with _timed("moma_ce_fwd"):
+            n = lib.moma_ce_workspace_bytes(B, K)
+            if n == 0:
+                raise ValueError(f"ce_head: logits {tuple(logits.shape)} are past the kernels' caps (B <= {_lib.CE_MAX_B}, "
+                                 f"K <= {_lib.CE_MAX_K})")
+            nw = (n + 7) // 8
+            # (one allocation: workspace, lse [B], 1 / n_valid; handed over as addresses -- three views of it would cost the host
+            #  more than the head's two launches take)
+            buf = torch.empty(nw + B + 1, device=dev, dtype=torch.float64)
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            base = buf.data_ptr()
+            check(lib.moma_ce_fwd(_ptr(logits), _ptr(labels), B, K, code, base, nw * 8, _ptr(loss), base + nw * 8, base + (nw + B) * 8,
+                                  None, _ptr(stats), _ptr(conf), _stream()), "moma_ce_fwd")
+        ctx.save_for_backward(logits, labels, buf)
+        ctx.meta = (code, nw)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        lib = _lib.load()
+        logits, labels, buf = ctx.saved_tensors
+        B, K = logits.shape
+        code, nw = ctx.meta
+        if g.dtype != torch.float32:                  # the upstream gradient stays on the device (a GradScaler factor rides in it)
+            g = g.to(torch.float32)
+        with _timed("moma_ce_bwd"):
+            dz = torch.empty((B, K), device=logits.device, dtype=logits.dtype)
+            base = buf.data_ptr()
+            check(lib.moma_ce_bwd(_ptr(logits), _ptr(labels), base + nw * 8, base + (nw + B) * 8, _ptr(g), _ptr(dz), B, K, code,
+                                  _stream()), "moma_ce_bwd")
+        return dz, None, None, None
+
+
+def ce_head(logits, labels, stats=None, conf=None) -> torch.Tensor:
+    """nn.CrossEntropyLoss()(logits, labels) -- the mean over the rows whose label is not -100 -- with the head's metrics from the same
+    two launches.  logits [B, K] float32 or bfloat16, contiguous; labels [B] int64 -> scalar float32.  stats (optional, [4] float64,
+    device): the call ADDS (sum of the valid rows' losses, top-1 hits, valid rows, rows with a bad label).  conf (optional, [K, K] int64,
+    device, row = label, column = prediction): the call adds 1 at [label, argmax] for every valid row; the argmax is the lowest index
+    of the row's maximum.  A label outside [0, K) other than -100 is never used as an index: the loss is NaN, the row's gradient zero
+    and stats[3] counts it (stock torch asserts on the device).  The gradient flows to the logits, in their dtype."""
+    # (the head's two launches take less than a dozen tensor queries do: one pass over the usual case, the reasons only when it fails)
+    ok = (torch.is_tensor(logits) and logits.is_cuda and logits.dim() == 2 and logits.dtype in _DT_CODES and logits.is_contiguous()
+          and logits.numel() > 0 and torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int64
+          and labels.shape == logits.shape[:1] and labels.is_contiguous())
+    if not ok:
+        _dev(logits, "logits", dtype=None, contiguous=False)
+        if logits.dim() != 2 or logits.dtype not in _DT_CODES:
+            raise TypeError(f"ce_head: logits must be a 2-D float32 / bfloat16 tensor, got {tuple(logits.shape)} {logits.dtype}")
+        if not logits.is_contiguous():
+            raise ValueError(f"ce_head: logits {tuple(logits.shape)} with strides {tuple(logits.stride())} are not contiguous")
+        _dev(labels, "labels", torch.int64)
+        if tuple(labels.shape) != (logits.shape[0],):
+            raise ValueError(f"ce_head: labels {tuple(labels.shape)} for logits {tuple(logits.shape)}")
+        raise ValueError(f"ce_head: empty logits {tuple(logits.shape)}")
+    K = logits.shape[1]
+    if stats is not None:
+        _dev(stats, "stats", torch.float64)
+        if tuple(stats.shape) != (4,):
+            raise ValueError(f"ce_head: stats {tuple(stats.shape)}, expected (4,)")
+    if conf is not None:
+        _dev(conf, "conf", torch.int64)
+        if tuple(conf.shape) != (K, K):
+            raise ValueError(f"ce_head: conf {tuple(conf.shape)}, expected {(K, K)}")
+    return _CEHead.apply(logits, labels, stats, conf)
+
+
+# ------------------------------------------------------------------------------------------------
 # What the losses on a B x B batch relation (rkd, sp, pkt: below) share: guards, the [B, D] view, the backward call
 # ------------------------------------------------------------------------------------------------
 def _rel_side(op, f, name):
