@@ -188,6 +188,13 @@ static_assert(pick_vec(6, 2, 0, {8, 4}) == 1 && pick_vec(8, 4, 0, {4, 4}) == 4, 
 static_assert(pick_vec(6, 2, 0, {8, 4, 2}) == 2 && pick_vec(112, 2, 4, {8, 4, 2}) == 2, "dw");
 // nst.hip, rkd.hip, sp.hip {16 / eb}: 16 bytes or nothing
 static_assert(pick_vec(12, 2, 0, {8}) == 1 && pick_vec(16, 2, 0, {8}) == 8 && pick_vec(16, 2, 8, {8}) == 1, "nst / rkd / sp");
+// mapwalk.hpp (vid.hip, hint.hip) and semckd.hip, per side: the widest of 8, 4, 1 elements that divides the contiguous extent and
+// whose accesses (16 bytes at most each) are aligned
+inline int side_vec(const void* p, long long extent, int dtype) {
+    if (dtype == MOMA_DT_BF16) return pick_vec((long)extent, 2, (uintptr_t)p, {8, 4});
+    const int v = pick_vec((long)extent, 4, (uintptr_t)p, {4});
+    return v == 4 && extent % 8 == 0 ? 8 : v;                                      // (8 fp32: two 16-byte accesses)
+}
 
 // ---- run-time (dtype, vec) -> template arguments (host; semckd.hip also on the device, per pair of a grouped launch) ---------
 // f(TypeTag<bf16_raw>{}) or f(TypeTag<float>{}) by MOMA_DT_*; inside a generic lambda: using T = typename decltype(t)::type

@@ -154,13 +154,6 @@ __global__ __launch_bounds__(REL_THREADS) void semckd_bwd_kernel(const SemTable 
     }
 }
 
-// the widest of 8, 4, 1 elements that divides n and whose accesses (16 bytes at most each) are aligned on this side
-int semckd_side_vec(const void* p, long long n, int dtype) {
-    if (dtype == MOMA_DT_BF16) return pick_vec((long)n, 2, (uintptr_t)p, {8, 4});
-    const int v = pick_vec((long)n, 4, (uintptr_t)p, {4});
-    return v == 4 && n % 8 == 0 ? 8 : v;                                           // (8 fp32: two 16-byte accesses)
-}
-
 long long semckd_chunks(long long n) { return (n + SEMCKD_CHUNK - 1) / SEMCKD_CHUNK; }
 
 SemTable semckd_table(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B, bool with_dx) {
@@ -168,8 +161,8 @@ SemTable semckd_table(const moma_semckd_pair_t* pairs, int n_pairs, int S, int B
     long long first = 0;
     for (int p = 0; p < n_pairs; ++p) {
         const moma_semckd_pair_t& a = pairs[p];
-        int v = min(semckd_side_vec(a.x, a.n, a.dtype_x), semckd_side_vec(a.t, a.n, a.dtype_t));
-        if (with_dx && a.dx) v = min(v, semckd_side_vec(a.dx, a.n, a.dtype_x));
+        int v = min(side_vec(a.x, a.n, a.dtype_x), side_vec(a.t, a.n, a.dtype_t));
+        if (with_dx && a.dx) v = min(v, side_vec(a.dx, a.n, a.dtype_x));
         tb.p[p] = SemPair{a.x, a.t, with_dx ? a.dx : nullptr, a.n, first, (int)semckd_chunks(a.n),
                           (a.dtype_x == MOMA_DT_BF16 ? 1 : 0) | (a.dtype_t == MOMA_DT_BF16 ? 2 : 0) | (v << 2)};
         first += (long long)B * tb.p[p].nchunk;

@@ -1507,17 +1507,18 @@ def nst_loss(f_s, f_t) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 # Variational Information Distillation: per-channel Gaussian NLL of a regressor's output   (distiller_zoo/VID.py, helper/loops_moma.py:145-149)
 # ------------------------------------------------------------------------------------------------
-def _vid_side(f, name):
-    """-> layout code of a dense [B,C,H,W] float32 / bfloat16 device tensor (contiguous or channels_last, taken as it lies)"""
+def _map_side(f, name, op, composite):
+    """-> layout code of a dense [B,C,H,W] float32 / bfloat16 device tensor (contiguous or channels_last, taken as it lies); the
+    messages name `op` and distiller_zoo's `composite`.  For the ops on csrc/mapwalk.hpp: vid_nll, hint_bn_relu_mse."""
     _dev(f, name, dtype=None, contiguous=False)
     if f.dim() != 4 or f.dtype not in _DT_CODES:
-        raise TypeError(f"vid_nll: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+        raise TypeError(f"{op}: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
     if f.is_contiguous():
         return _lib.LAYOUT_NCHW
     if f.is_contiguous(memory_format=torch.channels_last):
         return _lib.LAYOUT_NHWC
-    raise ValueError(f"vid_nll: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is neither contiguous nor channels_last "
-                     "(use distiller_zoo.VIDLoss.composite)")
+    raise ValueError(f"{op}: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is neither contiguous nor channels_last "
+                     f"(use distiller_zoo.{composite}.composite)")
 
 
 class _VIDNLL(torch.autograd.Function):
@@ -1526,7 +1527,7 @@ class _VIDNLL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mean, target, log_scale, eps):
         lib = _lib.load()
-        lay_m, lay_t = _vid_side(mean, "mean"), _vid_side(target, "target")
+        lay_m, lay_t = (_map_side(f, nm, "vid_nll", "VIDLoss") for f, nm in ((mean, "mean"), (target, "target")))
         _dev(log_scale, "log_scale", torch.float32)
         B, Cc, H, W = mean.shape
         if tuple(target.shape) != (B, Cc, H, W) or tuple(log_scale.shape) != (Cc,):
@@ -1595,19 +1596,6 @@ def hint_native(B: int, C: int, P: int, dtype=None, channels_last=None) -> bool:
     return True
 
 
-def _hint_side(f, name):
-    """-> layout code of a dense [B,C,H,W] float32 / bfloat16 device tensor (contiguous or channels_last, taken as it lies)"""
-    _dev(f, name, dtype=None, contiguous=False)
-    if f.dim() != 4 or f.dtype not in _DT_CODES:
-        raise TypeError(f"hint_bn_relu_mse: {name} must be a 4-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
-    if f.is_contiguous():
-        return _lib.LAYOUT_NCHW
-    if f.is_contiguous(memory_format=torch.channels_last):
-        return _lib.LAYOUT_NHWC
-    raise ValueError(f"hint_bn_relu_mse: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is neither contiguous nor "
-                     "channels_last (use distiller_zoo.ConvReg.composite)")
-
-
 class _HintBNReLUMSE(torch.autograd.Function):
     """hint_fwd (statistics, running statistics, loss, A and B) in the forward; hint_bwd (dx from the two maps and the saved [C]
     vectors, d weight and d bias from A and B) in the backward.  conv_bias only moves running_mean: its gradient is exact zeros."""
@@ -1615,7 +1603,7 @@ class _HintBNReLUMSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target, weight, bias, running_mean, running_var, momentum, eps, conv_bias):
         lib = _lib.load()
-        lay_x, lay_t = _hint_side(x, "x"), _hint_side(target, "target")
+        lay_x, lay_t = (_map_side(f, nm, "hint_bn_relu_mse", "ConvReg") for f, nm in ((x, "x"), (target, "target")))
         B, Cc, H, W = x.shape
         vecs = [("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var), ("conv_bias", conv_bias)]
         for nm, v in vecs:

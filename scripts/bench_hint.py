@@ -57,11 +57,12 @@ def inputs(B, C, H, W, dtype, mf, dev):
 def abi_times(x, t, gamma, beta, iters, warmup):
     """median us of each C-ABI call on preallocated buffers"""
     from moma_amd import _lib
-    from moma_amd.ops import _DT_CODES, _hint_side, _ptr, _stream
+    from moma_amd.ops import _DT_CODES, _map_side, _ptr, _stream
     lib = _lib.load()
     x, ga, be, dev = x.detach(), gamma.detach(), beta.detach(), x.device
     B, C, H, W = x.shape
-    codes = (_DT_CODES[x.dtype], _hint_side(x, "x"), _DT_CODES[t.dtype], _hint_side(t, "target"))
+    lay_x, lay_t = (_map_side(f, nm, "hint_bn_relu_mse", "ConvReg") for f, nm in ((x, "x"), (t, "target")))
+    codes = (_DT_CODES[x.dtype], lay_x, _DT_CODES[t.dtype], lay_t)
     n = lib.moma_hint_workspace_bytes(B, C, H * W, *codes)
     ws = torch.empty(n // 8, device=dev, dtype=torch.float64)
     mean, invstd = (torch.empty(C, device=dev, dtype=torch.float64) for _ in range(2))

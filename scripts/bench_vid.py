@@ -70,11 +70,12 @@ def step_of(fn, m, t, log_scale):
 def abi_times(m, t, log_scale, eps, iters, warmup):
     """median us of each C-ABI call on preallocated buffers"""
     from moma_amd import _lib
-    from moma_amd.ops import _DT_CODES, _ptr, _stream, _vid_side
+    from moma_amd.ops import _DT_CODES, _map_side, _ptr, _stream
     lib = _lib.load()
     m, ls, dev = m.detach(), log_scale.detach(), m.device
     B, C, H, W = m.shape
-    codes = (_DT_CODES[m.dtype], _vid_side(m, "mean"), _DT_CODES[t.dtype], _vid_side(t, "target"))
+    lay_m, lay_t = (_map_side(f, nm, "vid_nll", "VIDLoss") for f, nm in ((m, "mean"), (t, "target")))
+    codes = (_DT_CODES[m.dtype], lay_m, _DT_CODES[t.dtype], lay_t)
     n = lib.moma_vid_workspace_bytes(B, C, H * W, *codes)
     ws = torch.empty(n // 8, device=dev, dtype=torch.float64)
     sq, var, gls = (torch.empty(C, device=dev) for _ in range(3))
