@@ -493,6 +493,46 @@ int moma_ce_bwd(const void* z, const int64_t* labels, const double* lse, const d
                 int K, int dtype, moma_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * KDHEAD   The student's head of every `--distill` step -- replaces nn.CrossEntropyLoss(logit_s, y), DistillKL(T)(logit_s, logit_t)
+ *      (distiller_zoo/KD.py: two divisions, log_softmax, softmax, kl_div batchmean, times T^2), helper/util.accuracy (top-1) and the
+ *      .float() cast in front of them (helper/loops_moma.py:278-279), with their autograd backward to the student's logits.  For
+ *      z_s, z_t [B, K], labels y [B] and a host float T > 0, with a = z / T and p = softmax(a) per row:
+ *          m_b = max_k z_s[b,k]     pred_b = the LOWEST k with z_s[b,k] = m_b     (one maximum serves z_s and a_s: T > 0)
+ *          lse_b = logsumexp z_s[b,:]     lseS_b = logsumexp a_s[b,:]     lseT_b = logsumexp a_t[b,:]
+ *          ce_b = lse_b - z_s[b,y_b]                                              for a VALID row, 0 <= y_b < K
+ *          kl_b = sum_k p_t[b,k] (log p_t[b,k] - log p_s[b,k])                    (a term with p_t = 0 counts 0)
+ *          loss_cls = sum_valid ce_b / n_valid     loss_div = T^2 sum_b kl_b / B     acc = 100 #{b : pred_b == y_b} / B
+ *          dz_s[b,k] = g_cls (softmax(z_s)[b,k] - [k == y_b]) / n_valid           (zero for a row that is not valid)
+ *                    + g_div T (p_s[b,k] - p_t[b,k]) / B
+ *      Every logsumexp leaves the maximum's own term out of its sum and adds it back with log1p; kl_b is summed on the rows' shifted
+ *      values beside the teacher's sum of exponentials (no third walk over memory), so rows with z_t = z_s give exactly 0, in the loss
+ *      and in the KL part of dz_s.  Every sum, exponential and logarithm is double; the three lse and 1 / n_valid are kept in double.
+ *      z_s, z_t: MOMA_DT_F32 or MOMA_DT_BF16 INDEPENDENTLY, rows contiguous and dense, aligned to their element size (16-byte or
+ *      4-element accesses where both base addresses and K allow, element accesses otherwise); dz_s has z_s's dtype; z_t gets no
+ *      gradient.  labels: int64, by the rule of CE above: -100 is ignored (no CE term, left out of its mean, no CE gradient, never a
+ *      hit); ANY OTHER label outside [0, K) is never used as an index: it makes loss_cls NaN and its row's CE gradient zero.  The KL
+ *      term does not look at labels; acc divides by B, as helper/util.accuracy does.
+ *
+ * workspace        moma_kdhead_workspace_bytes(B, K) (8-byte aligned): the rows' CE and KL terms and flags between the two launches.
+ * moma_kdhead_fwd  -> out [3] fp32 = (loss_cls, loss_div, acc); saved [3 B + 1] double = lse [B], lseS [B], lseT [B], 1 / n_valid, for
+ *                  moma_kdhead_bwd.  Two launches: the rows (G lanes per row as CE; rows of up to MOMA_KDHEAD_ONE_WALK_K elements are
+ *                  read once for BOTH operands, longer ones twice), then ONE workgroup that adds the rows' terms in row order (256
+ *                  consecutive runs of rows, their sums in order) and rounds each result once.  No floating-point atomics: bitwise
+ *                  reproducible.  Nothing happens on the host but the argument checks.
+ * moma_kdhead_bwd  -> dz_s.  One launch, no reduction.  g_cls and g_div are DEVICE scalars (fp32); either may be NULL (= 0: that part
+ *                  is not evaluated), not both.  Both parts are multiplied and added in double before the one rounding: a power of two
+ *                  in both scales every bit pattern exactly.
+ *      B < 1, K < 1, or T not finite or <= 0: MOMA_E_SHAPE; unknown dtype: MOMA_E_DTYPE; B > MOMA_KDHEAD_MAX_B or K > MOMA_KDHEAD_MAX_K:
+ *      MOMA_E_UNSUPPORTED (CE's caps).  Nothing is launched and nothing written in any of these cases.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_KDHEAD_MAX_B = 16384, MOMA_KDHEAD_MAX_K = 32768, MOMA_KDHEAD_ONE_WALK_K = 1024 };
+size_t moma_kdhead_workspace_bytes(int B, int K);
+int moma_kdhead_fwd(const void* z_s, const void* z_t, const int64_t* labels, int B, int K, int dtype_s, int dtype_t, float T,
+                    void* workspace, size_t workspace_bytes, float* out, double* saved, moma_stream_t stream);
+int moma_kdhead_bwd(const void* z_s, const void* z_t, const int64_t* labels, const double* saved, const float* g_cls, const float* g_div,
+                    void* dz, int B, int K, int dtype_s, int dtype_t, float T, moma_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * RKDRelational Knowledge Distillation (`--distill rkd`) on one pair of feature rows -- replaces RKDLoss.forward
  *      (distiller_zoo/RKD.py: pdist -> smooth L1 of the mean-normalised distances, and unsqueeze-difference -> F.normalize -> bmm ->
  *      smooth L1 of the angles) and its autograd backward to f_s, without any [B, B, D] temporary.  For f_s [B, Ds], f_t [B, Dt]

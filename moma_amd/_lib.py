@@ -20,6 +20,7 @@ HINT_CHUNK = 1024
 SRRL_MAX_B, SRRL_MAX_C, SRRL_MAX_K = 1024, 4096, 1024
 CC_MAX_B, CC_MAX_C, CC_MAX_D = 1024, 4096, 4096
 CE_MAX_B, CE_MAX_K, CE_ONE_WALK_K = 16384, 32768, 1024
+KDHEAD_MAX_B, KDHEAD_MAX_K, KDHEAD_ONE_WALK_K = 16384, 32768, 1024
 RKD_MAX_B = 1024
 SP_MAX_B = 1024
 PKT_MAX_B = 1024
@@ -83,6 +84,9 @@ SIGNATURES = {
     "moma_ce_workspace_bytes": (_z, [_i, _i]),
     "moma_ce_fwd": (_i, [_p, _p, _i, _i, _i, _p, _z] + [_p] * 6 + [_p]),
     "moma_ce_bwd": (_i, [_p] * 6 + [_i] * 3 + [_p]),
+    "moma_kdhead_workspace_bytes": (_z, [_i, _i]),
+    "moma_kdhead_fwd": (_i, [_p] * 3 + [_i] * 4 + [_f, _p, _z, _p, _p] + [_p]),
+    "moma_kdhead_bwd": (_i, [_p] * 7 + [_i] * 4 + [_f] + [_p]),
     "moma_rkd_workspace_bytes": (_z, [_i]),
     "moma_rkd_dist": (_i, [_p, _i, _i, _i, _p, _p]),
     "moma_rkd_terms": (_i, [_p, _p, _i, _f, _f, _p, _z, _p, _p, _p, _p]),

@@ -1077,6 +1077,43 @@ int moma_ce_bwd(const void* z, const int64_t* labels, const double* lse, const d
     return hip_rc(launch_ce_bwd(z, labels, lse, inv_n, g_loss, dz, B, K, dtype, (hipStream_t)stream));
 }
 
+// ---- The student's head (cross-entropy, KD divergence at temperature T, top-1) ------------------------------------------------------
+static int kdhead_check(int B, int K, int dtype_s, int dtype_t, float T) {
+    if (B < 1 || K < 1 || !(T > 0.f) || !(T <= 3.402823466e+38f)) return MOMA_E_SHAPE;      // (a NaN fails both comparisons)
+    if (bad_dt(dtype_s) || bad_dt(dtype_t)) return MOMA_E_DTYPE;
+    if (B > MOMA_KDHEAD_MAX_B || K > MOMA_KDHEAD_MAX_K) return MOMA_E_UNSUPPORTED;
+    return MOMA_OK;
+}
+
+size_t moma_kdhead_workspace_bytes(int B, int K) {
+    if (kdhead_check(B, K, MOMA_DT_F32, MOMA_DT_F32, 1.f) != MOMA_OK) return 0;
+    return kdhead_workspace_bytes(B);
+}
+
+int moma_kdhead_fwd(const void* z_s, const void* z_t, const int64_t* labels, int B, int K, int dtype_s, int dtype_t, float T,
+                    void* workspace, size_t workspace_bytes, float* out, double* saved, moma_stream_t stream) {
+    if (!z_s || !z_t || !labels || !workspace || !out || !saved) return MOMA_E_NULL;
+    const int rc = kdhead_check(B, K, dtype_s, dtype_t, T);
+    if (rc != MOMA_OK) return rc;
+    if (workspace_bytes < kdhead_workspace_bytes(B)) return MOMA_E_WORKSPACE;
+    if (misaligned(z_s, dtype_s == MOMA_DT_BF16 ? 2 : 4) || misaligned(z_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(labels, 8) ||
+        misaligned(workspace, 8) || misaligned(out, 4) || misaligned(saved, 8))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_kdhead_fwd(z_s, z_t, labels, B, K, dtype_s, dtype_t, T, workspace, out, saved, (hipStream_t)stream));
+}
+
+int moma_kdhead_bwd(const void* z_s, const void* z_t, const int64_t* labels, const double* saved, const float* g_cls, const float* g_div,
+                    void* dz, int B, int K, int dtype_s, int dtype_t, float T, moma_stream_t stream) {
+    if (!z_s || !z_t || !labels || !saved || !dz || (!g_cls && !g_div)) return MOMA_E_NULL;
+    const int rc = kdhead_check(B, K, dtype_s, dtype_t, T);
+    if (rc != MOMA_OK) return rc;
+    const size_t es = dtype_s == MOMA_DT_BF16 ? 2 : 4;
+    if (misaligned(z_s, es) || misaligned(dz, es) || misaligned(z_t, dtype_t == MOMA_DT_BF16 ? 2 : 4) || misaligned(labels, 8) ||
+        misaligned(saved, 8) || misaligned(g_cls, 4) || misaligned(g_div, 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_kdhead_bwd(z_s, z_t, labels, saved, g_cls, g_div, dz, B, K, dtype_s, dtype_t, T, (hipStream_t)stream));
+}
+
 // ---- The losses on a B x B batch relation (rkd, sp, pkt): the guards they share ---------------------------------------------------
 // f [B, D] of `dtype` with lo <= B <= hi
 static int rel_check(int B, long long D, int dtype, int lo, int hi) {

@@ -25,31 +25,14 @@
 //   ce_bwd_kernel<T, VEC>         one thread per VEC elements of dz; no reduction.  g_loss is a DEVICE scalar multiplied in double before
 //             the one rounding to fp32 (and, for bf16, one more to the storage type): a power of two scales every bit pattern exactly.
 // hipcc -O3, gfx950 (-Rpass-analysis=kernel-resource-usage): see DESIGN.md, section CE; no kernel spills, none uses scratch.
-#include "common.hpp"
+#include "rowhead.hpp"
 
 namespace moma {
 namespace {
 
-constexpr int CE_THREADS = 256;
-constexpr int CE_PER_LANE = 16;                     // elements of a row one lane keeps in registers
-constexpr int CE_ONE_WALK = WAVE * CE_PER_LANE;     // longest row that is read once (MOMA_CE_ONE_WALK_K)
+// (rowhead.hpp: CE_THREADS, CE_PER_LANE, CE_ONE_WALK, CE_IGNORE, ce_ceil, ce_lanes, ce_take, ce_vec -- shared with kdhead.hip)
 static_assert(CE_ONE_WALK == MOMA_CE_ONE_WALK_K, "header and kernel agree on the one-walk limit");
 constexpr int CE_VALID = 1, CE_HIT = 2, CE_BAD = 4;
-constexpr long long CE_IGNORE = -100;               // nn.CrossEntropyLoss's ignore_index
-
-int ce_ceil(int a, int b) { return (a + b - 1) / b; }
-
-// lanes per row: the power of two (1 .. 64) that covers ceil(K / 16)
-int ce_lanes(int K) {
-    int g = 1;
-    while (g < WAVE && g * CE_PER_LANE < K) g *= 2;
-    return g;
-}
-
-// (value, index) of the larger value, the LOWER index among equals; a NaN never wins
-__device__ __forceinline__ void ce_take(float& bv, int& bi, float v, int i) {
-    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
 
 template <typename T, int VEC, bool ONE>
 __global__ __launch_bounds__(CE_THREADS) void ce_rows_kernel(const T* __restrict__ z, const long long* __restrict__ labels, int B, int K,
@@ -182,9 +165,6 @@ __global__ __launch_bounds__(CE_THREADS) void ce_bwd_kernel(const T* __restrict_
     }
     PV<T, VEC>::st(dz + at, v);
 }
-
-// the widths of a launch: 16 bytes (8 bf16 / 4 fp32), 4 elements, else element accesses
-template <typename T> int ce_vec(int K, uintptr_t low_bits) { return pick_vec(K, sizeof(T), low_bits, {MAXVEC<T>, 4}); }
 
 }  // namespace
 

@@ -333,6 +333,13 @@ hipError_t launch_ce_fwd(const void* z, const int64_t* labels, int B, int K, int
 hipError_t launch_ce_bwd(const void* z, const int64_t* labels, const double* lse, const double* inv_n, const float* g_loss, void* dz,
                          int B, int K, int dtype, hipStream_t st);
 
+// ---- kdhead.hip (the student's head: cross-entropy, the KD divergence at temperature T and top-1, the student logits' gradient) ------
+size_t kdhead_workspace_bytes(int B);
+hipError_t launch_kdhead_fwd(const void* z_s, const void* z_t, const int64_t* labels, int B, int K, int dt_s, int dt_t, float T,
+                             void* workspace, float* out, double* saved, hipStream_t st);
+hipError_t launch_kdhead_bwd(const void* z_s, const void* z_t, const int64_t* labels, const double* saved, const float* g_cls,
+                             const float* g_div, void* dz, int B, int K, int dt_s, int dt_t, float T, hipStream_t st);
+
 // ---- rkd.hip (Relational Knowledge Distillation: pairwise squared distances, the distance and angle terms, the student's gradient) --
 size_t rkd_workspace_bytes(int B);
 hipError_t launch_rkd_dist(const void* f, int B, long long D, int dtype, double* S, hipStream_t st);

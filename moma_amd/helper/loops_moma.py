@@ -98,6 +98,7 @@ from .util import AverageMeter, accuracy
 from ..learning.contrast_trainer import ContrastTrainer
 from ..learning.ddp import FlatDataParallel
 from .graphs import GraphedInference
+from .kd_head import StudentHead
 
 
 def _set_bn_train(m):
@@ -138,6 +139,9 @@ class MomaStep:
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(getattr(opt, "amp", None))
         self.scaler = getattr(opt, "_grad_scaler", None)
         self.fused = getattr(opt, "moma_fused", True)
+        # --student_head fused: one StudentHead at the divergence's temperature stands for criterion_cls, criterion_div and accuracy
+        # in losses_and_query (criterion_list keeps its three entries: validation and the checkpoints read them)
+        self.student_head = StudentHead(self.criterion_div.T) if getattr(opt, "student_head", "stock") == "fused" else None
         self.mocoatt = getattr(opt, "mem", "MoCo") == "MoCoAtt"
         self.attn_in_shuffle = (opt.distill == "moma" and getattr(opt, "attn", "self") in ("self_mix", "self_nomix")
                                 and not self.mocoatt)
@@ -236,8 +240,14 @@ class MomaStep:
         """CE + KL (:278-279), embed_s (:323-324), the query side of K1 (:326), the student's top-1
         -> dict(loss_cls, loss_div, f_s, k, all_k, acc, qp)"""
         opt, trainer, criterion_kd, contrast = self.opt, self.trainer, self.criterion_kd, self.contrast
-        logit_s = logit_s.float()
-        out = {"loss_cls": self.criterion_cls(logit_s, labels), "loss_div": self.criterion_div(logit_s, logit_t), "qp": None}
+        if self.student_head is not None:
+            # --student_head fused: CE, KL and the top-1 from one kernel pair, on the logits as the backbone left them (no .float())
+            loss_cls, loss_div, acc = self.student_head(logit_s, logit_t, labels)
+            out = {"loss_cls": loss_cls, "loss_div": loss_div, "qp": None}
+        else:
+            logit_s = logit_s.float()
+            out = {"loss_cls": self.criterion_cls(logit_s, labels), "loss_div": self.criterion_div(logit_s, logit_t), "qp": None}
+            acc = None
         f_s = None
         if opt.distill == "crd":
             f_s = feat_s[-1].float()                                                      # (:304)
@@ -281,7 +291,9 @@ class MomaStep:
                     qpack = contrast.qpack(f_s.shape[0], f_s.shape[1], f_s.device)
                 f_s = criterion_kd.atts_q(f_s, qpack=qpack)
                 out["qp"] = qpack
-        out.update(f_s=f_s, k=k, all_k=all_k, acc=accuracy(logit_s, labels, topk=(1,))[0].squeeze(0))
+        if acc is None:
+            acc = accuracy(logit_s, labels, topk=(1,))[0].squeeze(0)
+        out.update(f_s=f_s, k=k, all_k=all_k, acc=acc)
         return out
 
     def prefetch_queue(self):

@@ -104,7 +104,8 @@ class StepGraphs:
     def same_objects(self, st) -> bool:
         o = self.st
         return o is not None and o.model_s is st.model_s and o.model_t is st.model_t and o.criterion_kd is st.criterion_kd \
-            and o.contrast is st.contrast and o.optimizer is st.optimizer and o.trainer is st.trainer
+            and o.contrast is st.contrast and o.optimizer is st.optimizer and o.trainer is st.trainer \
+            and (o.student_head is None) == (st.student_head is None)       # (--student_head: g_query holds one head's launches)
 
     def bind(self, st) -> None:
         """`st`: the epoch's MomaStep (a new object per epoch over the same models).  The captured graphs stay valid -- they
@@ -134,7 +135,7 @@ class StepGraphs:
                 # attribute) makes this another variant -- never a replay through a stale pointer (~0.1 ms of host time per step)
                 hash(tuple(t.data_ptr() for t in self._state)),
                 st.contrast.T, st.amp_dtype, st.overlap, float(st.opt.cls), float(st.opt.div), float(st.opt.beta),
-                float(st.opt.alpha), float(getattr(st.criterion_div, "T", 0.0)))
+                float(st.opt.alpha), float(getattr(st.criterion_div, "T", 0.0)), st.student_head is not None)
 
     # ---- one step ---------------------------------------------------------------------------------------------------------
     def _switch(self, replayed: bool, device):

@@ -1997,6 +1997,111 @@ def ce_head(logits, labels, stats=None, conf=None) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# The student's head: cross-entropy, the KD divergence at temperature T and top-1   (helper/loops_moma.py:278-279, distiller_zoo/KD.py)
+# ------------------------------------------------------------------------------------------------
+def kd_head_native(B: int, K: int, dtype_s=None, dtype_t=None) -> bool:
+    """Shapes (batch B, classes K) whose cross-entropy, KD divergence and top-1 run on csrc/kdhead.hip; the others take
+    helper.kd_head.StudentHead.composite.  The kernels serve 1 <= B <= 16384 and 1 <= K <= 32768 (the C ABI's caps, the CE head's);
+    anything past them is refused here, so the module never asks the library for a shape it returns an error for.  By
+    profiles/kdhead_microbench.txt (B in (64, 256) x K in (4, 9, 100, 1000), fp32 and bf16 student logits against fp32 teacher logits,
+    forward + backward of the head against the stock chain with its .float() cast and accuracy; verdict: fused <= stock ops + the
+    stock form's own spread) all 16 rows hold, fp32 student logits included: 100 - 215 us against 234 - 351 us, 1.6 - 2.6 x.  The
+    stock chain here is 33 - 36 launches against the fused route's 9, so the Python backward node that cost the CE head its fp32 rows
+    is paid for several times over: no dtype pair is turned away.  `dtype_s` / `dtype_t`
+    describe the student's and the teacher's logits; asked without them the table answers for the shape alone."""
+    if not (1 <= B <= _lib.KDHEAD_MAX_B and 1 <= K <= _lib.KDHEAD_MAX_K):
+        return False
+    for dt in (dtype_s, dtype_t):
+        if dt is not None and dt not in _DT_CODES:
+            return False
+    return True
+
+
+class _KDHead(torch.autograd.Function):
+    """kdhead_fwd (loss_cls, loss_div, acc; the three lse and 1 / n_valid) in the forward; kdhead_bwd (one launch, no reduction) in the
+    backward, with the two upstream gradients as device scalars (None: a NULL pointer, that part is not evaluated)."""
+
+    @staticmethod
+    def forward(ctx, logit_s, logit_t, labels, T):
+        lib = _lib.load()
+        B, K = logit_s.shape
+        dev = logit_s.device
+        codes = (_DT_CODES[logit_s.dtype], _DT_CODES[logit_t.dtype])
+        ctx.set_materialize_grads(False)
+        with _timed("moma_kdhead_fwd"):
+            n = lib.moma_kdhead_workspace_bytes(B, K)
+            if n == 0:
+                raise ValueError(f"kd_head: logits {tuple(logit_s.shape)} are past the kernels' caps (B <= {_lib.KDHEAD_MAX_B}, "
+                                 f"K <= {_lib.KDHEAD_MAX_K})")
+            nw = (n + 7) // 8
+            # (one allocation: workspace, then lse, lseS, lseT [B] each and 1 / n_valid; handed over as addresses, as _CEHead does)
+            buf = torch.empty(nw + 3 * B + 1, device=dev, dtype=torch.float64)
+            out = torch.empty(3, device=dev, dtype=torch.float32)
+            base = buf.data_ptr()
+            check(lib.moma_kdhead_fwd(_ptr(logit_s), _ptr(logit_t), _ptr(labels), B, K, *codes, T, base, nw * 8, _ptr(out), base + nw * 8,
+                                      _stream()), "moma_kdhead_fwd")
+        ctx.save_for_backward(logit_s, logit_t, labels, buf)
+        ctx.meta = (codes, nw, T)
+        loss_cls, loss_div, acc = out.unbind(0)
+        ctx.mark_non_differentiable(acc)
+        return loss_cls, loss_div, acc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls, g_div, _g_acc):
+        if (g_cls is None and g_div is None) or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        lib = _lib.load()
+        logit_s, logit_t, labels, buf = ctx.saved_tensors
+        B, K = logit_s.shape
+        codes, nw, T = ctx.meta
+        # (the upstream gradients stay on the device: the loss weights and a GradScaler's factor ride in them)
+        if g_cls is not None and g_cls.dtype != torch.float32:
+            g_cls = g_cls.to(torch.float32)
+        if g_div is not None and g_div.dtype != torch.float32:
+            g_div = g_div.to(torch.float32)
+        with _timed("moma_kdhead_bwd"):
+            dz = torch.empty((B, K), device=logit_s.device, dtype=logit_s.dtype)
+            check(lib.moma_kdhead_bwd(_ptr(logit_s), _ptr(logit_t), _ptr(labels), buf.data_ptr() + nw * 8, _ptr(g_cls), _ptr(g_div), _ptr(dz),
+                                      B, K, *codes, T, _stream()), "moma_kdhead_bwd")
+        return dz, None, None, None
+
+
+def kd_head(logit_s, logit_t, labels, T):
+    """(nn.CrossEntropyLoss()(logit_s, labels), DistillKL(T)(logit_s, logit_t), helper.util.accuracy(logit_s, labels)[0]) from one
+    kernel pair.  logit_s, logit_t [B, K] float32 or bfloat16 (independently), contiguous; labels [B] int64; T a finite host float > 0
+    -> (loss_cls, loss_div, acc), scalar float32 each.  loss_cls is the mean over the rows whose label is not -100; a label outside
+    [0, K) other than -100 is never used as an index: loss_cls is NaN and that row's cross-entropy gradient zero (stock torch asserts
+    on the device).  loss_div = T^2 KL(softmax(logit_t / T) || softmax(logit_s / T)) summed over the rows and divided by B; it does
+    not look at labels.  acc = 100 x (rows whose lowest argmax equals their label) / B.  The gradients of loss_cls and loss_div flow to
+    logit_s, in its dtype; logit_t gets none and acc is not differentiable."""
+    # (one pass over the usual case, the reasons only when it fails: see ce_head)
+    ok = (torch.is_tensor(logit_s) and logit_s.is_cuda and logit_s.dim() == 2 and logit_s.dtype in _DT_CODES and logit_s.is_contiguous()
+          and logit_s.numel() > 0 and torch.is_tensor(logit_t) and logit_t.is_cuda and logit_t.dtype in _DT_CODES
+          and logit_t.shape == logit_s.shape and logit_t.is_contiguous() and torch.is_tensor(labels) and labels.is_cuda
+          and labels.dtype == torch.int64 and labels.shape == logit_s.shape[:1] and labels.is_contiguous())
+    if not ok:
+        for t, nm in ((logit_s, "logit_s"), (logit_t, "logit_t")):
+            _dev(t, nm, dtype=None, contiguous=False)
+            if t.dim() != 2 or t.dtype not in _DT_CODES:
+                raise TypeError(f"kd_head: {nm} must be a 2-D float32 / bfloat16 tensor, got {tuple(t.shape)} {t.dtype}")
+            if not t.is_contiguous():
+                raise ValueError(f"kd_head: {nm} {tuple(t.shape)} with strides {tuple(t.stride())} is not contiguous")
+        if logit_t.shape != logit_s.shape:
+            raise ValueError(f"kd_head: logit_t {tuple(logit_t.shape)} for logit_s {tuple(logit_s.shape)}")
+        _dev(labels, "labels", torch.int64)
+        if tuple(labels.shape) != (logit_s.shape[0],):
+            raise ValueError(f"kd_head: labels {tuple(labels.shape)} for logits {tuple(logit_s.shape)}")
+        raise ValueError(f"kd_head: empty logits {tuple(logit_s.shape)}")
+    T = float(T)
+    if not (0.0 < T < float("inf")):
+        raise ValueError(f"kd_head: the temperature must be finite and > 0, got {T}")
+    if logit_t.requires_grad and torch.is_grad_enabled():
+        raise ValueError("kd_head: the kernels give no gradient to logit_t (detach it, or use helper.kd_head.StudentHead.composite)")
+    return _KDHead.apply(logit_s, logit_t, labels, T)
+
+
+# ------------------------------------------------------------------------------------------------
 # What the losses on a B x B batch relation (rkd, sp, pkt: below) share: guards, the [B, D] view, the backward call
 # ------------------------------------------------------------------------------------------------
 def _rel_side(op, f, name):

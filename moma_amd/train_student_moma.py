@@ -41,7 +41,11 @@ and launch lines carry over.  What differs:
     available) feeds pre-generated batches of the same shape;
   * one process per GPU either through torchrun (RANK/LOCAL_RANK/WORLD_SIZE in the environment) or, as in the
     reference, `--multiprocessing-distributed` + mp.spawn; the backend string 'nccl' is RCCL on ROCm;
-  * new optional flags: --moma_prec, --queue_dtype, --amp, --channels_last, --shuffle_bn, --no_fused,
+  * `--student_head fused` (default `stock`): the cross-entropy, the KD divergence and the student's top-1 of every `--distill` step
+    -- nn.CrossEntropyLoss, DistillKL and helper.util.accuracy behind a .float() cast, about thirty small launches -- as ONE kernel
+    pair of csrc/kdhead.hip (helper/kd_head.py: StudentHead) on the logits in the dtype the backbones leave them (bf16 under
+    `--amp bf16`); with `--distill kd` that is the whole criterion side of the step.  Validation and checkpoints are unchanged;
+  * new optional flags: --moma_prec, --queue_dtype, --amp, --channels_last, --shuffle_bn, --no_fused, --student_head,
     --steps_per_epoch, --num_heads, --no_graph_teacher, --no_graph_student, --dp (student wrap at world size > 1: flat = one gradient all-reduce per step, the
     default; ddp = stock DistributedDataParallel as in the reference);
   * the reference's default run is cudnn.deterministic (a seed is set: :241-246; cudnn.benchmark only with its --deterministic
@@ -152,6 +156,10 @@ def build_parser():
     p.add_argument("--dp", default=None, choices=["flat", "ddp", "auto"],
                    help="student wrap at world size > 1: one flat gradient all-reduce per step (default) or stock DDP")
     p.add_argument("--no_fused", action="store_true", help="reference call sequence on materialised logits")
+    p.add_argument("--student_head", default="stock", choices=["stock", "fused"],
+                   help="cross-entropy, KD divergence and the student's top-1 of every step: stock = nn.CrossEntropyLoss + DistillKL + "
+                        "accuracy on float32 logits, fused = helper.kd_head.StudentHead, one kernel pair of csrc/kdhead.hip on the "
+                        "logits as the backbones leave them")
     p.add_argument("--steps_per_epoch", type=int, default=100, help="synthetic loader length")
     p.add_argument("--n_data", type=int, default=None,
                    help="--distill crd: samples in the training set = rows of the memory banks (default: steps_per_epoch * "
