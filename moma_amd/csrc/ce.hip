@@ -30,7 +30,7 @@
 namespace moma {
 namespace {
 
-// (rowhead.hpp: CE_THREADS, CE_PER_LANE, CE_ONE_WALK, CE_IGNORE, ce_ceil, ce_lanes, ce_take, ce_vec -- shared with kdhead.hip)
+// (rowhead.hpp: CE_THREADS, CE_PER_LANE, CE_ONE_WALK, CE_IGNORE, ce_lanes, ce_take, ce_vec -- shared with kdhead.hip)
 static_assert(CE_ONE_WALK == MOMA_CE_ONE_WALK_K, "header and kernel agree on the one-walk limit");
 constexpr int CE_VALID = 1, CE_HIT = 2, CE_BAD = 4;
 
@@ -177,7 +177,7 @@ hipError_t launch_ce_fwd(const void* z, const int64_t* labels, int B, int K, int
     int* row_pred = (int*)(row_loss + B);
     int* row_flag = row_pred + B;
     const int G = ce_lanes(K);
-    const dim3 grid(ce_ceil(B, CE_THREADS / G));
+    const dim3 grid(ceil_div(B, CE_THREADS / G));
     with_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         with_vec<MAXVEC<T>, 8, 4, 1>(ce_vec<T>(K, (uintptr_t)z), [&](auto vec) {

@@ -16,6 +16,8 @@ typedef unsigned short bf16_raw;  // storage type of a bf16 queue element
 
 constexpr int WAVE = 64;
 
+constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
 __device__ __forceinline__ float bf16_to_f32(bf16_raw v) {
     return __uint_as_float(((unsigned)v) << 16);
 }

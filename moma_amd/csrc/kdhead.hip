@@ -220,7 +220,7 @@ hipError_t launch_kdhead_fwd(const void* z_s, const void* z_t, const int64_t* la
     double* row_kl = row_ce + B;
     int* row_flag = (int*)(row_kl + B);
     const int G = ce_lanes(K);
-    const dim3 grid(ce_ceil(B, CE_THREADS / G));
+    const dim3 grid(ceil_div(B, CE_THREADS / G));
     const double inv_T = 1.0 / (double)T;
     with_dtype(dt_s, [&](auto ts) {
         using TS = typename decltype(ts)::type;

@@ -11,8 +11,6 @@ constexpr int CE_PER_LANE = 16;                     // elements of a row one lan
 constexpr int CE_ONE_WALK = WAVE * CE_PER_LANE;     // longest row that is read once (MOMA_CE_ONE_WALK_K, MOMA_KDHEAD_ONE_WALK_K)
 constexpr long long CE_IGNORE = -100;               // nn.CrossEntropyLoss's ignore_index
 
-inline int ce_ceil(int a, int b) { return (a + b - 1) / b; }
-
 // lanes per row: the power of two (1 .. 64) that covers ceil(K / 16)
 inline int ce_lanes(int K) {
     int g = 1;

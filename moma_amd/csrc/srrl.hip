@@ -16,17 +16,15 @@
 //             running statistics in place (unbiased variance B / (B - 1)).  The workgroup owns every row of its channels, so a second
 //             walk follows at once: xh = round((double(x) - mean) invstd), y = max(0, fma(gamma, xh, beta)) in fp32 -> y [B, C] and the
 //             channel's sum of (y - t)^2 in double.
-//   srrl_gemm_kernel<NT>   p's partial sums: 64 x 64 tile of [B, K], 4 x 4 outputs per thread from LDS tiles of y and W, plain fp32 FMA
-//             over one SEGMENT of 32 channels, the segment's sum then added to a DOUBLE total (gfx950 has no xf32; 1280 channels are
-//             40 segments); the next segment is requested while the current one is multiplied.  Shapes with few tiles split the
-//             channels over blockIdx.z (a function of the shape alone, about one workgroup per compute unit): partials
-//             [splits, B, K] in double.
+//   srrl_gemm_kernel<NT>   p's partial sums: the 64 x 64 tile product of tile64.hpp (fp32 FMA over a SEGMENT of 32 channels, the segment's
+//             sum added to a DOUBLE total) on y and W.  Shapes with few tiles split the channels over blockIdx.z (tile64_segs: a
+//             function of the shape alone, about one workgroup per compute unit): partials [splits, B, K] in double.
 //   srrl_pred_kernel   one workgroup per row: p = the splits added in order + b, rounded ONCE to fp32 (what the reference holds), e = p - l
 //             -> e [B, K] fp32 and the row's sum of e^2 in double.
 //   srrl_gemm_kernel<NN>   q = e W, the same kernel with W walked along its rows: partials [splits, B, C] in double.
 //   srrl_grad_kernel   srrl_bn_kernel's walk again: recomputes xh and y from x, dY = (y - t) 2 / (B C) + q 2 / (B K) and g in double,
 //             A and B in double in the order of the rows, then the second walk writes dxu = round(gamma invstd (g - A / B - xh B / B)) over
-//             y.  Workgroup 0 also adds the channels' and the rows' squared errors in order -> loss.
+//             y.  Workgroup 0 also adds the channels' and the rows' squared errors in order (tile64.hpp's ordered sum) -> loss.
 //   srrl_scale_kernel  (backward) dx = round(dxu g_loss) in x's dtype, d_gamma = g_loss B, d_beta = g_loss A: a power of two in g_loss
 //             scales every gradient exactly.
 // Five launches forward, one backward.  No atomics, every sum in a fixed order that depends on the shape alone: bitwise repeatable.
@@ -35,17 +33,14 @@
 //   values of the next segment in flight: 3 waves per SIMD) and 16.5 KB of LDS; srrl_pred_kernel 18 VGPRs, 32 B of LDS;
 //   srrl_grad_kernel 40 VGPRs, 4352 B of LDS; srrl_scale_kernel 10 VGPRs, no LDS.  8 waves per SIMD but for the GEMM.
 //   No kernel spills, none uses scratch.
-#include "common.hpp"
+#include "tile64.hpp"
 
 namespace moma {
 namespace {
 
-constexpr int SRRL_THREADS = 256;
+constexpr int SRRL_THREADS = T64_THREADS;           // (the loss in srrl_grad_kernel is tile64.hpp's ordered sum)
 constexpr int SRRL_TC = 16;                         // channels of a workgroup of the two batch walks
 constexpr int SRRL_RL = SRRL_THREADS / SRRL_TC;     // row lanes per channel
-constexpr int SRRL_TILE = 64;                       // outputs of a GEMM workgroup per side (4 x 4 per thread)
-constexpr int SRRL_SEG = 32;                        // elements of the reduction in one fp32 segment
-constexpr int SRRL_TARGET_WG = 256;                 // workgroups a GEMM aims at when it splits its reduction (one per compute unit)
 
 // the SRRL_RL row lanes of a channel meet in the order of tr; thread (0, tc) returns the sum
 __device__ __forceinline__ double srrl_rows_sum(double (*sh)[SRRL_TC], int tr, int tc, double v) {
@@ -113,82 +108,18 @@ __global__ __launch_bounds__(SRRL_THREADS) void srrl_bn_kernel(const TX* __restr
     if (tr == 0 && ok) colsum[c] = l;
 }
 
-// out[s, m, n] = sum over the split's k of A[m, k] Bm(n, k), Bm(n, k) = NN ? Bm[k N + n] : Bm[n Kr + k]; A [M, Kr] dense.
-// 64 x 64 outputs per workgroup, thread (ty, tx) owns rows ty + 16 i and columns tx + 16 j: the tiles lie in LDS as [row][k] with a
-// stride of 33 (the NN form's Bm as [k][n], stride 65), so the 16 columns of a wave's read fall into 16 banks and its 4 rows are
-// broadcasts.  The next segment's 16 values per thread are requested before the current one is multiplied.
+// out[s, m, n] = sum over the split's k of A[m, k] Bm(n, k), Bm(n, k) = NN ? Bm[k N + n] : Bm[n Kr + k]; A [M, Kr] dense: one tile of
+// tile64.hpp per workgroup, split s = blockIdx.z over `segs` segments of the reduction
 template <bool NN>
-__global__ __launch_bounds__(SRRL_THREADS) void srrl_gemm_kernel(const float* __restrict__ A, const float* __restrict__ Bm,
-                                                                 double* __restrict__ out, int M, int N, int Kr, int segs) {
-    constexpr int LD = SRRL_SEG + 1, LN = SRRL_TILE + 1, PER = SRRL_TILE * SRRL_SEG / SRRL_THREADS;
-    __shared__ float As[SRRL_TILE * LD], Bs[NN ? SRRL_SEG * LN : SRRL_TILE * LD];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int n0 = blockIdx.x * SRRL_TILE, m0 = blockIdx.y * SRRL_TILE, s = blockIdx.z;
-    const int kbeg = s * segs * SRRL_SEG, kend = min(Kr, kbeg + segs * SRRL_SEG);
-    float ra[PER], rb[PER];
-    auto request = [&](int k0) {
-#pragma unroll
-        for (int r = 0; r < PER; ++r) {
-            const int idx = tid + r * SRRL_THREADS;
-            {
-                const int gm = m0 + idx / SRRL_SEG, gk = k0 + idx % SRRL_SEG;
-                ra[r] = gm < M && gk < kend ? A[(size_t)gm * Kr + gk] : 0.f;
-            }
-            if constexpr (NN) {
-                const int gk = k0 + idx / SRRL_TILE, gn = n0 + idx % SRRL_TILE;
-                rb[r] = gk < kend && gn < N ? Bm[(size_t)gk * N + gn] : 0.f;
-            } else {
-                const int gn = n0 + idx / SRRL_SEG, gk = k0 + idx % SRRL_SEG;
-                rb[r] = gn < N && gk < kend ? Bm[(size_t)gn * Kr + gk] : 0.f;
-            }
-        }
-    };
+__global__ __launch_bounds__(T64_THREADS) void srrl_gemm_kernel(const float* __restrict__ A, const float* __restrict__ Bm,
+                                                                double* __restrict__ out, int M, int N, int Kr, int segs) {
+    __shared__ float As[T64_LDS], Bs[T64_LDS];
+    const int n0 = blockIdx.x * T64_TILE, m0 = blockIdx.y * T64_TILE, s = blockIdx.z;
+    const int kbeg = s * segs * T64_SEG, kend = min(Kr, kbeg + segs * T64_SEG);
     double dacc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dacc[i][j] = 0.0;
-    request(kbeg);
-    for (int k0 = kbeg; k0 < kend; k0 += SRRL_SEG) {
-#pragma unroll
-        for (int r = 0; r < PER; ++r) {
-            const int idx = tid + r * SRRL_THREADS;
-            As[(idx / SRRL_SEG) * LD + idx % SRRL_SEG] = ra[r];
-            if constexpr (NN) Bs[(idx / SRRL_TILE) * LN + idx % SRRL_TILE] = rb[r];
-            else Bs[(idx / SRRL_SEG) * LD + idx % SRRL_SEG] = rb[r];
-        }
-        __syncthreads();
-        if (k0 + SRRL_SEG < kend) request(k0 + SRRL_SEG);
-        float acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-#pragma unroll 8
-        for (int kk = 0; kk < SRRL_SEG; ++kk) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) av[i] = As[(ty + 16 * i) * LD + kk];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bv[j] = NN ? Bs[kk * LN + tx + 16 * j] : Bs[(tx + 16 * j) * LD + kk];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dacc[i][j] += (double)acc[i][j];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = m0 + ty + 16 * i, n = n0 + tx + 16 * j;
-            if (m < M && n < N) out[((size_t)s * M + m) * N + n] = dacc[i][j];
-        }
+    tile64_zero(dacc);
+    tile64<false, NN, false, float, float>(A, Bm, As, Bs, M, N, Kr, kbeg, kend, m0, n0, dacc);
+    tile64_each(dacc, m0, n0, M, N, [=](int m, int n, double v) { out[((size_t)s * M + m) * N + n] = v; });
 }
 
 // one workgroup per row b
@@ -280,18 +211,10 @@ __global__ __launch_bounds__(SRRL_THREADS) void srrl_grad_kernel(const TX* __res
             a.dxu[(size_t)b * C + c] = round_f32(f * (r.g - am - (double)r.xh * bm));
         }
     }
-    if (blockIdx.x == 0) {                                                         // the loss: thread i adds terms i, i + 256, ... in order
-        __shared__ double ls[SRRL_THREADS];
-        double u = 0.0, v = 0.0;
-        for (int i = tid; i < C; i += SRRL_THREADS) u += a.colsum[i];
-        for (int i = tid; i < B; i += SRRL_THREADS) v += a.rowsum[i];
-        ls[tid] = u * a.inv_bc + v * a.inv_bk;
-        __syncthreads();
-        if (tid == 0) {
-            double w = 0.0;
-            for (int i = 0; i < SRRL_THREADS; ++i) w += ls[i];
-            *a.loss = (float)w;
-        }
+    if (blockIdx.x == 0) {                                                         // the loss: both weighted sums per thread, then in order
+        const double u = strided_sum(a.colsum, C), v = strided_sum(a.rowsum, B);
+        const double w = ordered_sum(u * a.inv_bc + v * a.inv_bk);
+        if (tid == 0) *a.loss = (float)w;
     }
 }
 
@@ -310,20 +233,14 @@ __global__ __launch_bounds__(SRRL_THREADS) void srrl_scale_kernel(const float* _
     }
 }
 
-int srrl_ceil(int a, int b) { return (a + b - 1) / b; }
-
-// segments of 32 along the reduction that one workgroup of a GEMM [M, N] adds: all of them where the tiles alone fill the device
-int srrl_segs(int M, int N, int Kr) {
-    const int tiles = srrl_ceil(M, SRRL_TILE) * srrl_ceil(N, SRRL_TILE), nseg = srrl_ceil(Kr, SRRL_SEG);
-    const int want = max(1, min(nseg, SRRL_TARGET_WG / tiles));
-    return srrl_ceil(nseg, want);
-}
-int srrl_splits(int M, int N, int Kr) { return srrl_ceil(srrl_ceil(Kr, SRRL_SEG), srrl_segs(M, N, Kr)); }
+// segments of 32 along the reduction that one workgroup of a GEMM [M, N] adds, and the splits that makes
+int srrl_segs(int M, int N, int Kr) { return tile64_segs(tile64_tiles(M, N), ceil_div(Kr, T64_SEG)); }
+int srrl_splits(int M, int N, int Kr) { return ceil_div(ceil_div(Kr, T64_SEG), srrl_segs(M, N, Kr)); }
 
 template <bool NN>
 hipError_t srrl_gemm(const float* A, const float* Bm, double* out, int M, int N, int Kr, hipStream_t st) {
-    const dim3 grid(srrl_ceil(N, SRRL_TILE), srrl_ceil(M, SRRL_TILE), srrl_splits(M, N, Kr));
-    hipLaunchKernelGGL((srrl_gemm_kernel<NN>), grid, dim3(SRRL_THREADS), 0, st, A, Bm, out, M, N, Kr, srrl_segs(M, N, Kr));
+    const dim3 grid(ceil_div(N, T64_TILE), ceil_div(M, T64_TILE), srrl_splits(M, N, Kr));
+    hipLaunchKernelGGL((srrl_gemm_kernel<NN>), grid, dim3(T64_THREADS), 0, st, A, Bm, out, M, N, Kr, srrl_segs(M, N, Kr));
     return hipGetLastError();
 }
 
@@ -359,7 +276,7 @@ hipError_t launch_srrl_fwd(const void* x, const void* t, const float* W, const f
                            int dt_x, int dt_t, void* workspace, double* sums, float* dxu, float* loss, float* y_out, float* pred_out,
                            hipStream_t st) {
     const SrrlWs w = srrl_ws(workspace, B, C, K);
-    const unsigned cgrid = (unsigned)srrl_ceil(C, SRRL_TC);
+    const unsigned cgrid = (unsigned)ceil_div(C, SRRL_TC);
     with_dtype(dt_x, [&](auto tx) {
         return with_dtype(dt_t, [&](auto tt) {
             using TX = typename decltype(tx)::type;
@@ -397,7 +314,7 @@ hipError_t launch_srrl_bwd(const float* dxu, const double* sums, const float* g_
                            int C, int dt_x, hipStream_t st) {
     const long long n = (long long)B * C;
     const long long need = dx ? n : C;
-    const unsigned grid = (unsigned)max((long long)srrl_ceil(C, SRRL_THREADS), min((need + SRRL_THREADS - 1) / SRRL_THREADS, 2048LL));
+    const unsigned grid = (unsigned)max((long long)ceil_div(C, SRRL_THREADS), min((need + SRRL_THREADS - 1) / SRRL_THREADS, 2048LL));
     with_dtype(dt_x, [&](auto tx) {
         using TX = typename decltype(tx)::type;
         hipLaunchKernelGGL((srrl_scale_kernel<TX>), dim3(grid), dim3(SRRL_THREADS), 0, st, dxu, sums, g_loss, (TX*)dx, d_gamma, d_beta, n,

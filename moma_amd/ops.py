@@ -1695,13 +1695,13 @@ def srrl_native(B: int, C: int, K: int, dtype=None) -> bool:
     return True
 
 
-def _srrl_rows(f, name):
-    """-> dense [B, C] float32 / bfloat16 device tensor"""
+def _rows_side(op, f, name):
+    """-> dense [B, C] float32 / bfloat16 device tensor (the per-side guard of srrl_bn_relu_dual_mse, cc_embed_neighbour and kd_head)"""
     _dev(f, name, dtype=None, contiguous=False)
     if f.dim() != 2 or f.dtype not in _DT_CODES:
-        raise TypeError(f"srrl_bn_relu_dual_mse: {name} must be a 2-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
+        raise TypeError(f"{op}: {name} must be a 2-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
     if not f.is_contiguous():
-        raise ValueError(f"srrl_bn_relu_dual_mse: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is not contiguous")
+        raise ValueError(f"{op}: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is not contiguous")
     return f
 
 
@@ -1712,8 +1712,8 @@ class _SRRLTail(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target, cls_weight, cls_bias, logits, weight, bias, running_mean, running_var, momentum, eps):
         lib = _lib.load()
-        _srrl_rows(x, "x")
-        _srrl_rows(target, "target")
+        _rows_side("srrl_bn_relu_dual_mse", x, "x")
+        _rows_side("srrl_bn_relu_dual_mse", target, "target")
         B, Cc = x.shape
         K = cls_weight.shape[0] if isinstance(cls_weight, torch.Tensor) and cls_weight.dim() == 2 else -1
         for nm, v, shape in (("cls_weight", cls_weight, (K, Cc)), ("cls_bias", cls_bias, (K,)), ("logits", logits, (B, K)),
@@ -1805,16 +1805,6 @@ def cc_native(B: int, Cs: int, Ct: int, D: int, dtype=None) -> bool:
     return True
 
 
-def _cc_rows(f, name):
-    """-> dense [B, C] float32 / bfloat16 device tensor"""
-    _dev(f, name, dtype=None, contiguous=False)
-    if f.dim() != 2 or f.dtype not in _DT_CODES:
-        raise TypeError(f"cc_embed_neighbour: {name} must be a 2-D float32 / bfloat16 tensor, got {tuple(f.shape)} {f.dtype}")
-    if not f.is_contiguous():
-        raise ValueError(f"cc_embed_neighbour: {name} {tuple(f.shape)} with strides {tuple(f.stride())} is not contiguous")
-    return f
-
-
 class _CCEmbedNeighbour(torch.autograd.Function):
     """cc_fwd (the difference of both heads, the loss, G = d loss / d difference) in the forward; cc_bwd (one grouped launch: the three
     products on G and the bias sums, scaled by the upstream gradient) in the backward."""
@@ -1822,8 +1812,8 @@ class _CCEmbedNeighbour(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_s, x_t, w_s, b_s, w_t, b_t):
         lib = _lib.load()
-        _cc_rows(x_s, "x_s")
-        _cc_rows(x_t, "x_t")
+        _rows_side("cc_embed_neighbour", x_s, "x_s")
+        _rows_side("cc_embed_neighbour", x_t, "x_t")
         B, Cs = x_s.shape
         Ct = x_t.shape[1]
         D = w_s.shape[0] if isinstance(w_s, torch.Tensor) and w_s.dim() == 2 else -1
@@ -2081,12 +2071,8 @@ def kd_head(logit_s, logit_t, labels, T):
           and logit_t.shape == logit_s.shape and logit_t.is_contiguous() and torch.is_tensor(labels) and labels.is_cuda
           and labels.dtype == torch.int64 and labels.shape == logit_s.shape[:1] and labels.is_contiguous())
     if not ok:
-        for t, nm in ((logit_s, "logit_s"), (logit_t, "logit_t")):
-            _dev(t, nm, dtype=None, contiguous=False)
-            if t.dim() != 2 or t.dtype not in _DT_CODES:
-                raise TypeError(f"kd_head: {nm} must be a 2-D float32 / bfloat16 tensor, got {tuple(t.shape)} {t.dtype}")
-            if not t.is_contiguous():
-                raise ValueError(f"kd_head: {nm} {tuple(t.shape)} with strides {tuple(t.stride())} is not contiguous")
+        _rows_side("kd_head", logit_s, "logit_s")
+        _rows_side("kd_head", logit_t, "logit_t")
         if logit_t.shape != logit_s.shape:
             raise ValueError(f"kd_head: logit_t {tuple(logit_t.shape)} for logit_s {tuple(logit_s.shape)}")
         _dev(labels, "labels", torch.int64)
