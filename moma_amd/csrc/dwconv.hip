@@ -13,7 +13,11 @@
 //   * each lane owns one output column and a strip of R rows: a (R-1)*S+K tall input column per tap column is read
 //     once from LDS into registers and reused by the R outputs (10 LDS reads per output at K=5, R=4 instead of 25);
 //     consecutive lanes touch consecutive LDS words and store consecutive outputs; the taps of the plane's channel
-//     are wave-uniform (staged per item in LDS, read back as broadcasts).
+//     are wave-uniform (staged per item in LDS, read back as broadcasts);
+//   * the small planes (7 x 7, 14 x 14, stride 1: dw_small_kernel) are launched as about the resident waves, each looping over
+//     many items: an item's planes are one contiguous span, fetched with 16-byte vectors one item ahead of the stencil and
+//     scattered into the odd-pitch tile at the commit (see the kernel).  The strip kernels, the stride-2 backward-data and
+//     the backward-weight kernel still run an item as fill, stencil, stores in sequence.
 // backward-data, stride 1 = the same kernel on dy with the flipped filter; stride 2 = a gather in "phase" form: a
 // lane produces a 2x2 block of dx from a ceil(K/2)^2 window of dy (no divergence, no zero-insertion);
 // backward-weight = per-lane K*K fp32 accumulators over the strips of all planes a wave visits for one channel
@@ -101,6 +105,24 @@ __device__ __forceinline__ void fill_tile(float* tile, const T* __restrict__ src
     }
 }
 
+// VEC elements of T as one load of 16 / 8 / 4 / 2 bytes leaves them: raw words, so that a vector fetched for the NEXT item costs
+// VEC * sizeof(T) / 4 registers while the current item's stencil runs; get(j) = element j as fp32 (what PV<T, VEC>::ld gives)
+template <typename T, int VEC> struct RawVec {
+    static constexpr int BYTES = VEC * (int)sizeof(T), NW = (BYTES + 3) / 4;
+    unsigned w[NW];
+    __device__ __forceinline__ void ld(const T* p) {
+        if constexpr (BYTES == 16) { const uint4 a = *reinterpret_cast<const uint4*>(p); w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; }
+        else if constexpr (BYTES == 8) { const uint2 a = *reinterpret_cast<const uint2*>(p); w[0] = a.x; w[1] = a.y; }
+        else if constexpr (BYTES == 4) w[0] = *reinterpret_cast<const unsigned*>(p);
+        else w[0] = *reinterpret_cast<const unsigned short*>(p);
+    }
+    __device__ __forceinline__ float get(int j) const {
+        if constexpr (sizeof(T) == 4) return __uint_as_float(w[j]);
+        else if constexpr (VEC == 1) return __uint_as_float(w[0] << 16);
+        else return __uint_as_float((j & 1) ? (w[j >> 1] & 0xffff0000u) : (w[j >> 1] << 16));
+    }
+};
+
 // ssl[2p], ssl[2p+1] = scale, shift of plane plane0 + p's channel, p < np <= 8 (forward kernels: an item's planes can belong
 // to different channels)
 __device__ __forceinline__ void stage_scale_shift(float* ssl, const float* __restrict__ ss, int plane0, int np, int C, int lane) {
@@ -187,13 +209,28 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_fwd_kernel(const T* __restri
 // (plane, output row): it reads its K input rows ((OWT-1)*S + K values each) from the tile once, keeps them in
 // registers together with the K*K taps of its plane, and produces the OWT outputs of the row fully unrolled:
 // (K*((OWT-1)*S+K) + K*K) LDS reads and OWT*K*K FMAs per OWT outputs (K=5, OWT=14: 8.2 reads per output instead of 15).
+//
+// The planes of an item are one contiguous span of memory (PB * H * W elements: 784 B at 7 x 7, 1568 B at 14 x 14 in bf16), so
+// the span is fetched with VEC-element vectors that ignore the row ends (VEC = the widest of 16 / 8 / 4 bytes that the span's
+// length and the base address allow, else elements) and scattered into the odd-pitch tile element by element at the commit.
+// The fetch of the wave's NEXT item (planes, taps, scale / shift pairs) is issued into registers before the stencil of the
+// current one and committed to the tile after it: a wave has bytes in flight all the time, not only while it fills.  Only
+// whole items are fetched that way (all PB planes present; the host launches VEC > 1 only where the span fits small_nv
+// vectors per lane); the ragged last item, shapes that do not fit and spans that only allow element loads take fill_tile's
+// path with nothing in flight ahead.  No fetch is issued for an
+// item that does not exist, and none reads past its item's span.
+constexpr int small_pb(int OWT) { return OWT == 7 ? 8 : 4; }
+constexpr int small_nv(int OWT, int VEC) { return (small_pb(OWT) * OWT * OWT + VEC * 64 - 1) / (VEC * 64); }
+
 template <typename T, int K, int S, int OWT, bool FLIP, int VEC, bool PRE>
-__global__ __launch_bounds__(DW_WAVES * 64) void dw_small_kernel(const T* __restrict__ x, const float* __restrict__ w,
+__global__ __launch_bounds__(DW_WAVES * 64, 4) void dw_small_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                                T* __restrict__ y, DwShape sh, const float* __restrict__ ss,
                                                                int act) {
     static_assert(!(PRE && FLIP), "the prologue belongs to the forward convolution");
     extern __shared__ float smem[];
     constexpr int IW = (OWT - 1) * S + K;        // input columns one output row needs
+    constexpr int NV = small_nv(OWT, VEC);       // vectors of the span per lane
+    constexpr int NT = (small_pb(OWT) * K * K + 63) / 64;        // taps per lane
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tfl = sh.PB * sh.IR * sh.pitch;
     const int wfl = (sh.PB * K * K + 3) & ~3;
@@ -203,15 +240,135 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_small_kernel(const T* __rest
     for (int i = lane; i < tfl; i += 64) tile[i] = 0.f;          // padding rows / columns stay zero for good
     const int p = lane / OWT, oy = lane - p * OWT;               // this lane's plane (of the item) and output row
     const int cbase = XO - sh.pl;
-    for (int item = uniform(blockIdx.x * DW_WAVES + wave); item < sh.ngroups; item += gridDim.x * DW_WAVES) {
-        const int plane0 = item * sh.PB, np = min(sh.PB, sh.NC - plane0);
-        for (int i = lane; i < np * K * K; i += 64) {
-            const int pp = i / (K * K), t = i - pp * (K * K);
-            wl[i] = w[((plane0 + pp) % sh.C) * K * K + (FLIP ? K * K - 1 - t : t)];
+    const int hw = sh.H * sh.W, span = sh.PB * hw, ntaps = sh.PB * K * K;
+    const float inv_hw = 1.0f / (float)hw, inv_w = 1.0f / (float)sh.W;
+    const int stride = gridDim.x * DW_WAVES;
+
+    // Where a vector of the span goes does not depend on the item, so each of this lane's NV vectors keeps one descriptor for the
+    // whole kernel.  A vector is at most one element longer than a row (the host launches VEC > 1 only with VEC <= W + 1),
+    // so one row end at most falls inside it:
+    //   bits 0..15  LDS byte address of its first element (the workgroup's LDS is 64 KiB at most)
+    //   bits 16..19 jw = its elements in front of the row end (VEC: none);  bit 20: that row end is also the plane's end
+    //   bits 21..   the plane of its first element
+    // Elements j >= jw sit `jump` bytes further on: the rest of the tile row, and of the plane's tile rows behind a plane's end.
+    // With 16-byte vectors the descriptors are kept in registers; the narrower widths (more vectors per lane) work them out again
+    // at every commit, which keeps every instantiation within the registers of 4 waves per SIMD.
+    constexpr bool KEEP = VEC * sizeof(T) == 16;
+    // element loads keep fill_tile's schedule, nothing is fetched ahead; nor for the prologue at 8- and 4-byte vectors, which with
+    // the vectors of the next item in registers does not fit 4 waves per SIMD without spilling (K = 5, 14 x 14)
+    constexpr bool PF = VEC > 1 && (KEEP || !PRE);
+    const int jump_row = (sh.pitch - sh.W) * 4, jump_plane = jump_row + (sh.IR - sh.H) * sh.pitch * 4;
+    auto describe = [&](int u, int ln) {
+        const int e = min((u * 64 + ln) * VEC, span - VEC);
+        const int pp = fast_div(e, hw, inv_hw), rem = e - pp * hw;
+        const int r = fast_div(rem, sh.W, inv_w), c = rem - r * sh.W;
+        const int idx = (int)(tile - smem) + (pp * sh.IR + r + sh.pt) * sh.pitch + XO + c;
+        const int jw = min(sh.W - c, VEC);
+        return (unsigned)idx * 4u | (unsigned)jw << 16 | (unsigned)(jw < VEC && r == sh.H - 1) << 20 | (unsigned)pp << 21;
+    };
+    [[maybe_unused]] unsigned desc[NV];
+#pragma unroll
+    for (int u = 0; u < NV; ++u) desc[u] = KEEP ? describe(u, lane) : 0u;
+
+    RawVec<T, VEC> xv[NV];                       // the fetched item: span vectors, taps, this lane's plane's scale / shift
+    float wv[NT];
+    [[maybe_unused]] float sv[2];
+    // a whole item that exists (wave-uniform)
+    auto whole = [&](int it) { return PF && it < sh.ngroups && ((long)it + 1) * sh.PB <= (long)sh.NC; };
+    // (fetch and commit work their addresses out from a lane number the compiler cannot see through: a handful of instructions
+    // per item instead of registers that would stay live across the stencil)
+    auto fetch = [&](int it) {
+        const int plane0 = it * sh.PB, c0 = plane0 % sh.C;
+        int lane = threadIdx.x & 63;
+        asm volatile("" : "+v"(lane));
+        const T* src = x + (size_t)plane0 * hw;
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            const int e = (u * 64 + lane) * VEC;
+#pragma unroll
+            for (int j = 0; j < RawVec<T, VEC>::NW; ++j) xv[u].w[j] = 0u;
+            if (e < span) xv[u].ld(src + e);     // VEC | span: a vector that starts inside the span ends inside it
         }
-        if constexpr (PRE) stage_scale_shift(ssl, ss, plane0, np, sh.C, lane);
-        fill_tile<T, VEC, PRE>(tile, x + (size_t)plane0 * sh.H * sh.W, (size_t)sh.H * sh.W, np, sh.H, sh.W, -sh.pt, sh.IR, sh.pitch,
-                               XO, lane, false, ssl, 2, act);
+#pragma unroll
+        for (int u = 0; u < NT; ++u) {
+            const int i = u * 64 + lane;
+            wv[u] = 0.f;
+            if (i < ntaps) {
+                const int pp = i / (K * K), t = i - pp * (K * K);
+                int c = c0 + pp;                 // (the host launches VEC > 1 only with PB <= C)
+                c -= c >= sh.C ? sh.C : 0;
+                wv[u] = w[c * K * K + (FLIP ? K * K - 1 - t : t)];
+            }
+        }
+        if constexpr (PRE) {
+            sv[0] = sv[1] = 0.f;
+            if (lane < sh.PB) {
+                int c = c0 + lane;
+                c -= c >= sh.C ? sh.C : 0;
+                sv[0] = ss[2 * c];
+                sv[1] = ss[2 * c + 1];
+            }
+        }
+    };
+    auto commit = [&]() {
+        int lane = threadIdx.x & 63;
+        asm volatile("" : "+v"(lane));
+#pragma unroll
+        for (int u = 0; u < NT; ++u)
+            if (u * 64 + lane < ntaps) wl[u * 64 + lane] = wv[u];
+        if constexpr (PRE) {
+            if (lane < sh.PB) { ssl[2 * lane] = sv[0]; ssl[2 * lane + 1] = sv[1]; }
+        }
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            if ((u * 64 + lane) * VEC < span) {
+                unsigned d;
+                if constexpr (KEEP) {
+                    asm volatile("" : "+v"(desc[u]));            // (or the fields are unpacked ahead of the loop, into registers)
+                    d = desc[u];
+                } else {
+                    d = describe(u, lane);
+                }
+                const int jw = (int)(d >> 16 & 15u);
+                const bool pend = d >> 20 & 1u;
+                char* a0 = reinterpret_cast<char*>(smem) + (d & 0xffffu);
+                char* a1 = a0 + (pend ? jump_plane : jump_row);
+                [[maybe_unused]] float sc0 = 0.f, sf0 = 0.f, sc1 = 0.f, sf1 = 0.f;
+                [[maybe_unused]] const int jb = pend ? jw : VEC;                 // elements j >= jb belong to the next plane
+                if constexpr (PRE) {
+                    const int pp = (int)(d >> 21), q = min(pp + 1, sh.PB - 1);
+                    sc0 = ssl[2 * pp]; sf0 = ssl[2 * pp + 1];
+                    sc1 = ssl[2 * q]; sf1 = ssl[2 * q + 1];
+                }
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    float v = xv[u].get(j);
+                    if constexpr (PRE) v = storage_round<T>(act_fwd(fmaf(v, j >= jb ? sc1 : sc0, j >= jb ? sf1 : sf0), act));
+                    *reinterpret_cast<float*>((j >= jw ? a1 : a0) + 4 * j) = v;
+                }
+            }
+        }
+    };
+
+    int item = uniform(blockIdx.x * DW_WAVES + wave);
+    bool have = whole(item);
+    if (have) fetch(item);
+    for (; item < sh.ngroups; item += stride) {
+        const int plane0 = item * sh.PB, np = min(sh.PB, sh.NC - plane0);
+        if (have) {
+            commit();
+        } else {
+            for (int i = lane; i < np * K * K; i += 64) {
+                const int pp = i / (K * K), t = i - pp * (K * K);
+                wl[i] = w[((plane0 + pp) % sh.C) * K * K + (FLIP ? K * K - 1 - t : t)];
+            }
+            if constexpr (PRE) stage_scale_shift(ssl, ss, plane0, np, sh.C, lane);
+            fill_tile<T, 1, PRE>(tile, x + (size_t)plane0 * hw, (size_t)hw, np, sh.H, sh.W, -sh.pt, sh.IR, sh.pitch, XO, lane, false,
+                                 ssl, 2, act);
+        }
+        // the next item's loads go out now and land while this item's stencil runs; its registers are free (just committed)
+        have = whole(item + stride);
+        if (have) fetch(item + stride);
         __builtin_amdgcn_s_waitcnt(0xc07f);
         if (p < np) {
             float wk[K * K];
@@ -235,7 +392,7 @@ __global__ __launch_bounds__(DW_WAVES * 64) void dw_small_kernel(const T* __rest
 #pragma unroll
             for (int ox = 0; ox < OWT; ++ox) st1<T>(o + ox, acc[ox]);
         }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_s_waitcnt(0xc07f);      // tile reads done before the next item is committed over it
     }
 }
 
@@ -426,6 +583,13 @@ unsigned grid_for(long nitems) {
     if (g > 256 * 16) g = 256 * 16;                // grid-stride beyond 16 workgroups per CU
     return (unsigned)max(1L, g);
 }
+// dw_small_kernel fetches one item ahead: launch about the waves that are resident at once (4 per SIMD by registers), so that
+// every wave loops over many items with a fetch in flight, not 16 workgroups per CU with two or three items each
+constexpr int SMALL_WG_PER_CU = 4;
+unsigned grid_small(long nitems) {
+    const long g = (nitems + DW_WAVES - 1) / DW_WAVES;
+    return (unsigned)max(1L, min(g, 256L * SMALL_WG_PER_CU));
+}
 
 // y (OH x OW) from x (H x W); also backward-data stride 1 with flip = true (then x = dy and y = dx)
 template <typename T, int K, int S>
@@ -435,29 +599,41 @@ hipError_t fwd_t(const T* x, const float* w, T* y, int NC, int C, int H, int W, 
     DwShape sh{};
     sh.NC = NC; sh.C = C; sh.H = H; sh.W = W; sh.OH = OH; sh.OW = OW; sh.pt = pt; sh.pl = pl;
     sh.pitch = round4(XO + max(W, (OW - 1) * S + K - pl) + 1);
-    if (S == 1 && OH == OW && (OW == 7 || OW == 14)) {
-        // small planes: one output row per lane, whole planes per item (stride 2 measured faster on the strip kernel)
-        sh.TH = OH; sh.nbands = 1;
-        sh.IR = (OH - 1) * S + K;
-        sh.PB = OW == 7 ? 8 : 4;
-        sh.pitch |= 1;           // lanes read rows one pitch apart: an odd pitch spreads them over all LDS banks
-        sh.ngroups = (NC + sh.PB - 1) / sh.PB;
-        // the kernel is chosen on the size WITHOUT the prologue's scale / shift pairs: the call with them takes the kernel (and the
-        // summation order) of the call without, or fails
-        const size_t lds0 = (size_t)DW_WAVES * (sh.PB * sh.IR * sh.pitch + round4(sh.PB * K * K)) * sizeof(float);
-        const size_t lds = lds0 + (ss ? (size_t)DW_WAVES * round4(2 * sh.PB) * sizeof(float) : 0);
-        if (lds0 <= (size_t)LDS_BUDGET) {
-            if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
-            const dim3 grid(grid_for(sh.ngroups)), block(DW_WAVES * 64);
-            const int vec = 1;       // (odd pitch: element stores into the tile; the wider instantiations below are never launched)
+    if constexpr (S == 1) {      // (no stride-2 instantiation of dw_small_kernel: stride 2 is faster on the strip kernel)
+        if (OH == OW && (OW == 7 || OW == 14)) {
+            // small planes: one output row per lane, whole planes per item
+            sh.TH = OH; sh.nbands = 1;
+            sh.IR = (OH - 1) * S + K;
+            sh.PB = OW == 7 ? 8 : 4;
+            sh.pitch |= 1;           // lanes read rows one pitch apart: an odd pitch spreads them over all LDS banks
+            sh.ngroups = (NC + sh.PB - 1) / sh.PB;
+            // the kernel is chosen on the size WITHOUT the prologue's scale / shift pairs: the call with them takes the kernel (and the
+            // summation order) of the call without, or fails
+            const size_t lds0 = (size_t)DW_WAVES * (sh.PB * sh.IR * sh.pitch + round4(sh.PB * K * K)) * sizeof(float);
+            const size_t lds = lds0 + (ss ? (size_t)DW_WAVES * round4(2 * sh.PB) * sizeof(float) : 0);
+            if (lds0 <= (size_t)LDS_BUDGET) {
+                if (lds > (size_t)LDS_BUDGET) return hipErrorInvalidValue;
+                // the span of a whole item as vectors: the widest width that divides its length (so every item starts aligned and no
+                // vector crosses the span's end) at an aligned base; whatever the width, the tile gets the same values
+                const long span = (long)sh.PB * H * W;
+                int vec = pick_vec(span, sizeof(T), (uintptr_t)x, {MAXVEC<T>, 4, 2});
+                // (every image row has a tile row and the planes of an item are at most one turn of the channels: what the
+                // fetch relies on)
+                auto fits = [&](int v) {
+                    const long nv = OW == 7 ? small_nv(7, v) : small_nv(14, v);
+                    return span <= nv * v * 64 && v <= W + 1 && pt >= 0 && H + pt <= sh.IR && sh.PB <= C;
+                };
+                if (!fits(vec)) vec = 1;     // VEC > 1 in the kernel means: whole items are fetched ahead as span vectors
+                const dim3 grid(grid_small(sh.ngroups)), block(DW_WAVES * 64);
 #define MOMA_DW_SMALL(OWT, FL, PR) \
     hipLaunchKernelGGL((dw_small_kernel<T, K, S, OWT, FL, V, PR>), grid, block, lds, st, x, w, y, sh, ss, act)
-            with_vec<MAXVEC<T>, 8, 4, 2, 1>(vec, [&](auto V) {
-                if (OW == 7) { if (flip) MOMA_DW_SMALL(7, true, false); else if (ss) MOMA_DW_SMALL(7, false, true); else MOMA_DW_SMALL(7, false, false); }
-                else { if (flip) MOMA_DW_SMALL(14, true, false); else if (ss) MOMA_DW_SMALL(14, false, true); else MOMA_DW_SMALL(14, false, false); }
-            });
+                with_vec<MAXVEC<T>, 8, 4, 2, 1>(vec, [&](auto V) {
+                    if (OW == 7) { if (flip) MOMA_DW_SMALL(7, true, false); else if (ss) MOMA_DW_SMALL(7, false, true); else MOMA_DW_SMALL(7, false, false); }
+                    else { if (flip) MOMA_DW_SMALL(14, true, false); else if (ss) MOMA_DW_SMALL(14, false, true); else MOMA_DW_SMALL(14, false, false); }
+                });
 #undef MOMA_DW_SMALL
-            return hipGetLastError();
+                return hipGetLastError();
+            }
         }
     }
     const int R = strip_rows(OH);
