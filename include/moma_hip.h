@@ -888,6 +888,34 @@ int moma_se_gate_fwd(const void* x, const void* s, void* out, int NC, int HW, in
 int moma_se_gate_bwd(const void* x, const void* s, const void* dout, void* dx, void* ds, int NC, int HW,
                      int dtype, moma_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * IN   the input batch: raw uint8 rows of a data pack -> the tensor the backbones read -- replaces, per batch, the tail of the
+ *      reference's transforms (dataset/histo_dataset.py:194-239 and :1054-1058: RandomHorizontalFlip, CenterCrop,
+ *      RandomResizedCrop, ToTensor, Normalize) and the layout / dtype passes behind them.  One launch, no workspace, no atomics.
+ *          src   uint8 [N, H, W, 3]                         idx   int64 [B], or NULL: sample b is row b of src
+ *          flip  uint8 [B], or NULL: none                   box   int32 [B, 4] = (top, left, h, w), or NULL: the centred S_h x S_w
+ *          lut   fp32 [3, 256]: lut[c][v] = ((v / 255) - mean_c) / std_c, built by the caller in ToTensor's and Normalize's order
+ *          out   [B, 3, S_h, S_w] of `dtype`, dense in MOMA_LAYOUT_NCHW or MOMA_LAYOUT_NHWC (channels_last memory)
+ *      The centred window has CenterCrop's offsets: (H - S_h) / 2 and (W - S_w) / 2, a half rounded to the even neighbour.
+ *      resample = 0   out[b, c, y, x] = lut[c][ src[idx_b, top + y, left + x', c] ],  x' = S_w - 1 - x where flip[b], else x; the
+ *                     box's h, w are not read.  S_h > H or S_w > W: MOMA_E_SHAPE.
+ *      resample = 1   bilinear over the box onto S_h x S_w with half-pixel centres: the source coordinate of output o is
+ *                     (o + 0.5) h / S - 0.5 clamped to [0, h - 1], the second tap clamped to h - 1, columns likewise.  The taps'
+ *                     weights are kept as integers over 2 S (exact); the four products are summed in fp32 (at most five roundings
+ *                     of a value <= 255: 7.7e-5) and the result becomes a level by floor(v + 0.5), which then goes through lut.
+ *                     Flip mirrors the output column.  h, w are taken into [1, H], [1, W].  A NULL box is the centred window, so
+ *                     the same as resample = 0.
+ *      Every read is clamped into sample idx_b's own image (rows to [0, H - 1], columns to [0, W - 1]; idx_b to [0, N - 1]).  Every
+ *      output element is a value of lut, or its bf16 rounded to nearest even.  src needs no alignment; out is aligned to its element
+ *      size (16-byte stores wherever an output row allows, element stores at its unaligned ends).
+ *      B == 0: MOMA_OK, nothing done.  Any other size < 1, or resample not 0 / 1: MOMA_E_SHAPE; unknown dtype or layout: MOMA_E_DTYPE;
+ *      H, W, S_h or S_w above MOMA_INPUT_MAX_SIDE, or S_h or S_w above MOMA_INPUT_MAX_RESAMPLE with resample = 1: MOMA_E_UNSUPPORTED.
+ *      Nothing is launched in any of these cases.
+ * ------------------------------------------------------------------------------------------- */
+enum { MOMA_INPUT_MAX_SIDE = 16384, MOMA_INPUT_MAX_RESAMPLE = 4096 };
+int moma_input_batch(const uint8_t* src, const int64_t* idx, const uint8_t* flip, const int32_t* box, const float* lut, void* out,
+                     int N, int H, int W, int B, int S_h, int S_w, int resample, int dtype, int layout, moma_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

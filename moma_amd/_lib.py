@@ -26,6 +26,7 @@ SP_MAX_B = 1024
 PKT_MAX_B = 1024
 SEMCKD_MAX_PAIRS, SEMCKD_CHUNK = 64, 4096
 MHA_SAVE_PROBS, MHA_SAVE_LSE = 0, 1
+INPUT_MAX_SIDE, INPUT_MAX_RESAMPLE = 16384, 4096
 ABI_VERSION = 4
 EMA_BLOCK_ELEMS = 4096
 
@@ -135,6 +136,7 @@ SIGNATURES = {
     "moma_bn_gate_bwd": (_i, [_p] * 11 + [_z] + [_i] * 6 + [_p]),
     "moma_mha_bwd_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "moma_mha_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
+    "moma_input_batch": (_i, [_p] * 6 + [_i] * 9 + [_p]),
 }
 
 

@@ -1307,4 +1307,22 @@ int moma_pkt_bwd(const void* f_s, const double* M, const float* g_loss, void* dF
     return hip_rc(launch_pkt_bwd(f_s, M, g_loss, dF_s, B, D, dtype, (hipStream_t)stream));
 }
 
+// ---- The input batch (uint8 rows of a data pack -> the normalised image tensor) -----------------------------------------------------
+int moma_input_batch(const uint8_t* src, const int64_t* idx, const uint8_t* flip, const int32_t* box, const float* lut, void* out,
+                     int N, int H, int W, int B, int S_h, int S_w, int resample, int dtype, int layout, moma_stream_t stream) {
+    if (!src || !lut || !out) return MOMA_E_NULL;
+    if (N < 0 || H < 0 || W < 0 || B < 0 || S_h < 0 || S_w < 0 || (resample != 0 && resample != 1)) return MOMA_E_SHAPE;
+    if (bad_dt(dtype) || (layout != MOMA_LAYOUT_NCHW && layout != MOMA_LAYOUT_NHWC)) return MOMA_E_DTYPE;
+    if (B == 0) return MOMA_OK;
+    if (N < 1 || H < 1 || W < 1 || S_h < 1 || S_w < 1) return MOMA_E_SHAPE;
+    if (H > MOMA_INPUT_MAX_SIDE || W > MOMA_INPUT_MAX_SIDE || S_h > MOMA_INPUT_MAX_SIDE || S_w > MOMA_INPUT_MAX_SIDE)
+        return MOMA_E_UNSUPPORTED;
+    if (!box) resample = 0;                                    // (the centred window at its own size: nothing to resample)
+    if (!resample && (S_h > H || S_w > W)) return MOMA_E_SHAPE;
+    if (resample && (S_h > MOMA_INPUT_MAX_RESAMPLE || S_w > MOMA_INPUT_MAX_RESAMPLE)) return MOMA_E_UNSUPPORTED;
+    if (misaligned(idx, 8) || misaligned(box, 4) || misaligned(lut, 4) || misaligned(out, dtype == MOMA_DT_BF16 ? 2 : 4))
+        return MOMA_E_ALIGN;
+    return hip_rc(launch_input_batch(src, idx, flip, box, lut, out, N, H, W, B, S_h, S_w, resample, dtype, layout, (hipStream_t)stream));
+}
+
 }  // extern "C"

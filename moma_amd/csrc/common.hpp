@@ -468,4 +468,9 @@ hipError_t launch_se_gate_fwd(const void* x, const void* s, void* out, int NC, i
 hipError_t launch_se_gate_bwd(const void* x, const void* s, const void* dout, void* dx, void* ds, int NC, int HW, int dtype,
                               hipStream_t st);
 
+// ---- input.hip (the input batch: uint8 rows of a data pack -> normalised fp32 / bf16 images, NCHW or channels_last) -------------
+hipError_t launch_input_batch(const uint8_t* src, const int64_t* idx, const uint8_t* flip, const int32_t* box, const float* lut,
+                              void* out, int N, int H, int W, int B, int Sh, int Sw, int resample, int dtype, int layout,
+                              hipStream_t st);
+
 }  // namespace moma

@@ -4,6 +4,8 @@ network downloads (out of scope); benchmarks and smoke runs us
 pre-generated on the target device so the loader never sits in the timed region."""
 import torch
 
+from .contrast import contrast_indices
+
 
 class SyntheticLoader:
     def __init__(self, n_batches, batch_size, image_size, n_cls, seed=12345, device="cpu", distinct=2,
@@ -62,17 +64,8 @@ class SyntheticSampleLoader:
         return self.n_batches
 
     def _contrast_idx(self, index, labels):
-        B = index.shape[0]
-        u = torch.rand(B, self.nce_k, device=self.device, generator=self.gen, dtype=torch.float64)
-        if self.mode == "exact":
-            cnt, start = self.counts[labels].unsqueeze(1), self.starts[labels].unsqueeze(1)
-            r = (u * (self.n_data - cnt)).long().clamp_(max=self.n_data - 1)
-            r = torch.minimum(r, self.n_data - cnt - 1)
-            neg = self.order[torch.where(r < start, r, r + cnt)]                 # skip the segment of the sample's own class
-        else:
-            r = (u * (self.n_data - 1)).long().clamp_(max=self.n_data - 2)
-            neg = torch.where(r < index.unsqueeze(1), r, r + 1)                  # skip the sample itself
-        return torch.cat([index.unsqueeze(1), neg], dim=1)
+        return contrast_indices(index, labels, self.order, self.counts, self.starts, self.n_data, self.nce_k, self.mode, self.gen,
+                                self.device)
 
     def __iter__(self):
         B = self.batch_size

@@ -2447,3 +2447,70 @@ def pkt_loss(f_s, f_t) -> torch.Tensor:
     if f_s.shape[0] > _lib.PKT_MAX_B:
         raise ValueError(f"pkt_loss: the kernels take 1 .. {_lib.PKT_MAX_B} rows, got {f_s.shape[0]}")
     return _PKTLoss.apply(f_s, f_t)
+
+
+# ------------------------------------------------------------------------------------------------
+# The input batch: uint8 rows of a data pack -> the tensor the backbones read   (dataset/histo_dataset.py:194-239, :1054-1058)
+# ------------------------------------------------------------------------------------------------
+def input_lut(mean, std, device=None) -> torch.Tensor:
+    """lut [3, 256] float32: lut[c][v] is what ToTensor + Normalize make of level v in channel c, in their order of operations
+    (v / 255, minus the mean, over the std; each rounded to float32), so the kernel's outputs equal theirs bit for bit."""
+    v = torch.arange(256, dtype=torch.float32)
+    rows = [v.div(255).sub(float(m)).div(float(s)) for m, s in zip(mean, std)]
+    if len(rows) != 3:
+        raise ValueError("input_lut: mean and std have three entries each")
+    lut = torch.stack(rows).contiguous()
+    return lut if device is None else lut.to(device)
+
+
+def input_batch(src, lut, size, idx=None, flip=None, box=None, resample=False, batch=None, dtype=torch.float32,
+                channels_last=False, out=None) -> torch.Tensor:
+    """src uint8 [N, H, W, 3] (device, contiguous) -> [B, 3, S_h, S_w] of `dtype` (float32 or bfloat16), contiguous or, with
+    `channels_last`, in torch.channels_last strides; one launch of csrc/input.hip.  `size` is S or (S_h, S_w).  idx int64 [B]: the
+    rows of src (None: rows 0 .. B - 1, B = `batch` or N); flip uint8 / bool [B] (None: none); box int32 [B, 4] = (top, left, h, w)
+    (None: the centred window, CenterCrop's offsets).  resample False: the S_h x S_w window at (top, left); True: the box resampled
+    bilinearly onto S_h x S_w.  `out`: a destination of that shape, dtype and memory format instead of a new tensor.  See
+    include/moma_hip.h (IN) for the arithmetic."""
+    lib = _lib.load()
+    _dev(src, "src", torch.uint8)
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"input_batch: src must be [N, H, W, 3], got {tuple(src.shape)}")
+    _dev(lut, "lut", torch.float32)
+    if tuple(lut.shape) != (3, 256):
+        raise ValueError(f"input_batch: lut must be [3, 256], got {tuple(lut.shape)}")
+    if dtype not in _DT_CODES:
+        raise TypeError(f"input_batch: dtype must be float32 or bfloat16, got {dtype}")
+    N, H, W = src.shape[:3]
+    Sh, Sw = (size, size) if isinstance(size, int) else size
+    B = None
+    for t, name, dt, shape in ((idx, "idx", torch.int64, None), (flip, "flip", None, None), (box, "box", torch.int32, 4)):
+        if t is None:
+            continue
+        _dev(t, name, dt)
+        if name == "flip" and t.dtype not in (torch.uint8, torch.bool):
+            raise TypeError(f"input_batch: flip must be uint8 or bool, got {t.dtype}")
+        if t.dim() != (1 if shape is None else 2) or (shape is not None and t.shape[1] != shape):
+            raise ValueError(f"input_batch: {name} has shape {tuple(t.shape)}")
+        if B is not None and t.shape[0] != B:
+            raise ValueError(f"input_batch: {name} has {t.shape[0]} rows, the batch {B}")
+        B = t.shape[0]
+    if batch is not None:
+        if B is not None and B != batch:
+            raise ValueError(f"input_batch: batch = {batch} but the operands have {B} rows")
+        B = batch
+    if B is None:
+        B = N
+    if idx is None and B > N:
+        raise ValueError(f"input_batch: a batch of {B} from {N} rows needs idx")
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    if out is None:
+        out = torch.empty((B, 3, Sh, Sw), device=src.device, dtype=dtype, memory_format=fmt)
+    else:
+        _dev(out, "out", dtype, contiguous=False)
+        if tuple(out.shape) != (B, 3, Sh, Sw) or not out.is_contiguous(memory_format=fmt):
+            raise ValueError(f"input_batch: out must be a dense [{B}, 3, {Sh}, {Sw}] tensor in the requested memory format")
+    with _timed("moma_input_batch"):
+        check(lib.moma_input_batch(_ptr(src), _ptr(idx), _ptr(flip), _ptr(box), _ptr(lut), _ptr(out), N, H, W, B, Sh, Sw,
+                                   1 if resample else 0, _DT_CODES[dtype], _lib.LAYOUT_NHWC if channels_last else _lib.LAYOUT_NCHW,
+                                   _stream()), "moma_input_batch")
+    return out

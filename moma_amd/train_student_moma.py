@@ -37,8 +37,11 @@ and launch lines carry over.  What differs:
     Representation Distillation, the method MoMA is defined against: moma_amd/crd/ on the gather kernels of csrc/crd.hip;
     `--nce_k / --nce_t / --nce_m / --mode` as in the reference, the synthetic sample loader, `--n_data` to size the banks) are
     built -- the other comparison criteria are out of scope (SURVEY section 2);
-  * real datasets need author-local folders; `--dataset synthetic` (default when the requested dataset is not
-    available) feeds pre-generated batches of the same shape;
+  * the reference's dataset lists point at author-local folders: `--data_pack PATH` trains on a pack of uint8 images written by
+    `python -m moma_amd.dataset.make_pack` (dataset/pack.py; `--aug_train NULL` = flip, `RRC` = random-resized-crop with `--crop` +
+    flip, both inside ONE launch of csrc/input.hip per batch together with ToTensor, Normalize, layout and dtype; `RA` is not built
+    and raises; `--data_device gpu | host`, `--input_dtype`; crd's `n_data` and negatives come from the pack); without the flag the
+    synthetic loaders feed pre-generated batches of the same shape (`--steps_per_epoch`);
   * one process per GPU either through torchrun (RANK/LOCAL_RANK/WORLD_SIZE in the environment) or, as in the
     reference, `--multiprocessing-distributed` + mp.spawn; the backend string 'nccl' is RCCL on ROCm;
   * `--student_head fused` (default `stock`): the cross-entropy, the KD divergence and the student's top-1 of every `--distill` step
@@ -73,6 +76,7 @@ import torch.optim as optim
 from .MoMA.mem_moco import build_mem
 from .MoMA.criterion_moco_att import CMO
 from .crd import CRDLoss
+from .dataset import pack
 from .dataset.synthetic import SyntheticLoader, SyntheticSampleLoader
 from .distiller_zoo import (PKT, SRRL, Attention, ConvReg, Correlation, DistillKL, HintLoss, LinearEmbed, NSTLoss, RKDLoss, SelfA,
                             SemCKDLoss, Similarity, VIDLoss)
@@ -108,7 +112,7 @@ def build_parser():
     p.add_argument("--model_t", type=str, default="effiB0")
     p.add_argument("--path_t", type=str, default=None, help="teacher model snapshot")
     # augment
-    p.add_argument("--aug_train", type=str, default="RA", choices=["NULL", "RA"])
+    p.add_argument("--aug_train", type=str, default="RA", choices=["NULL", "RA", "RRC"])
     p.add_argument("--crop", type=float, default=0.2)
     p.add_argument("--image_size", type=int, default=512)
     p.add_argument("--image_resize", action="store_true")
@@ -181,6 +185,7 @@ def build_parser():
     p.add_argument("--save_root", type=str, default="./save")
     p.add_argument("--resume", type=str, default=None,
                    help="checkpoint written by this trainer (ckpt_last.pth): student, EMA teacher, CMO, queue + pointer, optimizer")
+    pack.add_arguments(p)
     return p
 
 
@@ -452,6 +457,8 @@ def main_worker(gpu, ngpus_per_node, opt):
     device = torch.device("cuda", opt.gpu) if torch.cuda.is_available() else torch.device("cpu")
     opt.device = device
     print("opt.n_cls: ", opt.n_cls)
+    if opt.data_pack:                                            # (before anything is built: --distill crd sizes its banks by the pack)
+        pack.prepare(opt, IMAGE_SIZE.get(opt.dataset, opt.image_size))
 
     model_s, model_t, module_list, criterion_list, trainable_list, contrast, optimizer = build_training(opt, device)
     if contrast is not None:
@@ -470,12 +477,16 @@ def main_worker(gpu, ngpus_per_node, opt):
 
     size = IMAGE_SIZE.get(opt.dataset, opt.image_size)
     seed = (opt.seed or 0) + opt.rank
-    if opt.distill == "crd":
+    if opt.data_pack:
+        train_loader, val_loader, test_loader = pack.build_loaders(opt, size, device, sample=opt.distill == "crd")
+    elif opt.distill == "crd":
         train_loader = SyntheticSampleLoader(opt.steps_per_epoch, opt.batch_size, size, opt.n_cls, opt.nce_k, opt.mode, seed, device,
                                              n_data=opt.n_data)
     else:
         train_loader = SyntheticLoader(opt.steps_per_epoch, opt.batch_size, size, opt.n_cls, seed, device)
-    val_loader = SyntheticLoader(max(1, opt.steps_per_epoch // 10), opt.batch_size, size, opt.n_cls, seed + 1, device)
+    if not opt.data_pack:
+        val_loader = SyntheticLoader(max(1, opt.steps_per_epoch // 10), opt.batch_size, size, opt.n_cls, seed + 1, device)
+        test_loader = val_loader                                 # (the synthetic set doubles as test)
     is_main = (not opt.multiprocessing_distributed) or opt.rank % ngpus_per_node == 0
     if is_main:
         os.makedirs(opt.save_folder, exist_ok=True)
@@ -509,6 +520,8 @@ def main_worker(gpu, ngpus_per_node, opt):
     for epoch in range(start_epoch, opt.epochs + 1):
         adjust_learning_rate(epoch, opt, optimizer)
         print("==> training...")
+        if opt.data_pack:
+            train_loader.set_epoch(epoch)
         t1 = time.time()
         train_acc, train_loss = train_distill_moma(epoch, train_loader, module_list, criterion_list,
                                                    trainer if opt.distill in ("moma", "crd", "vid", "hint", "semckd", "srrl", "correlation") else None, contrast, optimizer, opt)
@@ -524,8 +537,8 @@ def main_worker(gpu, ngpus_per_node, opt):
                 epoch, train_acc, train_loss, t2 - t1, ips))
         val_acc, val_loss, val_stat = validate_distill(val_loader, module_list, criterion_list[0], opt, prefix="Val")
         test_acc = test_loss = test_stat = None
-        if not opt.skip_test:                                    # reference :515-519 (the synthetic set doubles as test)
-            test_acc, test_loss, test_stat = validate_distill(val_loader, module_list, criterion_list[0], opt, prefix="Test")
+        if not opt.skip_test:                                    # reference :515-519
+            test_acc, test_loss, test_stat = validate_distill(test_loader, module_list, criterion_list[0], opt, prefix="Test")
         if is_main:
             val_f1 = macro_f1(val_stat["conf_mat"])               # model selection by accuracy AND by macro-F1 (:522-571)
             print(" ** Acc_val@1 {:.3f}  F1_val {:.4f}".format(val_acc, val_f1))

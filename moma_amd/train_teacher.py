@@ -12,7 +12,9 @@ file imports its loops from a module that does not exist (helper.loops_RFF, :29)
 helper/loops_moma.py and are served here by helper/loops_vanilla.py.  What differs:
   * the criterion is helper.ce_head.CrossEntropyHead: loss, top-1 and the confusion matrix on the kernels of csrc/ce.hip with a device
     meter instead of two `.item()` reads per step; `--no_fused` restores nn.CrossEntropyLoss + helper.util.accuracy;
-  * real datasets need author-local folders: the synthetic loader feeds batches of the same shape (`--steps_per_epoch`);
+  * the reference's dataset lists point at author-local folders: `--data_pack PATH` trains on a pack of uint8 images (dataset/pack.py:
+    `--aug_train NULL` = flip, `RRC` = random-resized-crop + flip, both inside one launch of csrc/input.hip per batch; `RA` is not
+    built); without it the synthetic loader feeds batches of the same shape (`--steps_per_epoch`);
   * one process per GPU through torchrun or, as in the reference, `--multiprocessing-distributed` + spawn of fresh processes; the
     parent of the ranks counts the GPUs from sysfs (devices.visible_gpu_count) and never opens the device; the model is wrapped by
     learning/ddp.py's wrap_student (`--dp`);
@@ -35,6 +37,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
+from .dataset import pack  # noqa: E402
 from .dataset.synthetic import SyntheticLoader  # noqa: E402
 from .helper.ce_head import CrossEntropyHead  # noqa: E402
 from .helper.loops_moma import macro_f1  # noqa: E402
@@ -73,7 +76,7 @@ def build_parser():
     p.add_argument("--pretrain", type=str, default="PANDA", help="a local checkpoint file, or a name (random init)")
     p.add_argument("--pre_strict", action="store_false", help="strict by default")
     # augment
-    p.add_argument("--aug_train", type=str, default="RA", choices=["NULL", "RA"], help="aug_train")
+    p.add_argument("--aug_train", type=str, default="RA", choices=["NULL", "RA", "RRC"], help="aug_train")
     p.add_argument("--crop", type=float, default=0.2, help="crop threshold for RandomResizedCrop")
     p.add_argument("--image_size", type=int, default=512, help="image_size")
     p.add_argument("--image_resize", action="store_true")
@@ -99,6 +102,7 @@ def build_parser():
     p.add_argument("--resume", type=str, default=None, help="checkpoint written by this trainer (ckpt_last.pth)")
     p.add_argument("--no_fused", action="store_true",
                    help="nn.CrossEntropyLoss + helper.util.accuracy, the reference's sequence, instead of the fused head")
+    pack.add_arguments(p)
     return p
 
 
@@ -148,6 +152,8 @@ def main_worker(gpu, ngpus_per_node, opt):
     device = torch.device("cuda", opt.gpu) if torch.cuda.is_available() else torch.device("cpu")
     opt.device = device
     print("opt.n_cls:", opt.n_cls)
+    if opt.data_pack:
+        pack.prepare(opt, IMAGE_SIZE.get(opt.dataset, opt.image_size))
 
     model = load_model(opt.model, opt.pretrain, opt.n_cls, opt.pre_strict, opt.gpu, opt.multiprocessing_distributed)     # (:177)
     criterion = nn.CrossEntropyLoss() if opt.no_fused else CrossEntropyHead(opt.n_cls, meter=True)                         # (:184)
@@ -165,9 +171,12 @@ def main_worker(gpu, ngpus_per_node, opt):
 
     size = IMAGE_SIZE.get(opt.dataset, opt.image_size)
     seed = (opt.seed or 0) + opt.rank
-    train_loader = SyntheticLoader(opt.steps_per_epoch, opt.batch_size, size, opt.n_cls, seed, device)
-    val_loader = SyntheticLoader(max(1, opt.steps_per_epoch // 10), opt.batch_size, size, opt.n_cls, seed + 1, device)
-    test_loader = val_loader                                            # (the synthetic set doubles as test)
+    if opt.data_pack:
+        train_loader, val_loader, test_loader = pack.build_loaders(opt, size, device)
+    else:
+        train_loader = SyntheticLoader(opt.steps_per_epoch, opt.batch_size, size, opt.n_cls, seed, device)
+        val_loader = SyntheticLoader(max(1, opt.steps_per_epoch // 10), opt.batch_size, size, opt.n_cls, seed + 1, device)
+        test_loader = val_loader                                        # (the synthetic set doubles as test)
     is_main = (not opt.multiprocessing_distributed) or opt.rank % ngpus_per_node == 0
     if is_main:
         os.makedirs(opt.save_folder, exist_ok=True)
@@ -196,6 +205,8 @@ def main_worker(gpu, ngpus_per_node, opt):
     for epoch in range(start_epoch, opt.epochs + 1):
         adjust_learning_rate(epoch, opt, optimizer)
         print("==> training...")
+        if opt.data_pack:
+            train_loader.set_epoch(epoch)
         time1 = time.time()
         train_acc, train_loss = train(epoch, train_loader, model, criterion, optimizer, opt)
         if device.type == "cuda":
